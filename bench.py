@@ -436,6 +436,55 @@ def bench_small_reads(fa, comp, st, nb, n_ch, n_samp, x):
             "single_read_us": round(single * 1e6, 1), "batch_of_100_us": round(b100 * 1e6, 1), "batch_of_100_slices_per_s": round(100 / b100, 0)}
 
 
+DUMP_SAMPLES = 1 << 21  # positions per sampled array: 16 MiB of decoded samples (float64) + 8 MiB of compressed bytes (float32)
+DUMP_SEED = 20240601
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def block_sums(torch, flat, block):
+    """Exact int64 sums of consecutive `block`-element runs of a flat integer tensor (the last run may be short),
+    a few hundred MiB of int64 at a time."""
+    n = flat.numel()
+    out = torch.empty(-(-n // block), dtype=torch.int64, device=flat.device)
+    per = max(1, (64 << 20) // block)  # whole blocks per chunk
+    for b0 in range(0, out.numel(), per):
+        seg = flat[b0 * block : min(n, (b0 + per) * block)].to(torch.int64)
+        full = seg.numel() // block
+        if full:
+            out[b0 : b0 + full] = seg[: full * block].view(full, block).sum(dim=1)
+        if seg.numel() > full * block:
+            out[b0 + full] = seg[full * block :].sum()
+    return out
+
+
+def dump_outputs(torch, out_dir, comp, st, nb, y, n_samp):
+    """--dump-outputs: what the timed path hands its caller after the last step -- the encoder's (compressed, starts,
+    nbytes) triple and the decoder's array -- as DIR/<name>.npy (float32 / float64; exact while a channel's sum stays
+    below 2^53, i.e. up to 2^22 samples per channel), so that two
+    builds can be compared output for output.  starts and nbytes are written whole; the compressed bytes and the
+    decoded samples as a fixed, seeded sample of flat positions plus sums that cover every element (per 1 MiB block of
+    the blob, per channel of the decoded array)."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(t, seed):
+        flat = t.reshape(-1)
+        idx = np.sort(np.random.default_rng([DUMP_SEED, seed]).integers(0, flat.numel(), size=min(DUMP_SAMPLES, flat.numel())))
+        return flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+
+    arrays = {
+        "stream_starts": st.reshape(-1).cpu().numpy().astype(np.float64),
+        "stream_nbytes": nb.reshape(-1).cpu().numpy().astype(np.float64),
+        "compressed_sample": sample(comp, 1).astype(np.float32),
+        "compressed_block_sums": block_sums(torch, comp.reshape(-1), 1 << 20).cpu().numpy().astype(np.float64),
+        "decoded_sample": sample(y, 2).astype(np.float64),
+        "decoded_channel_sums": block_sums(torch, y.reshape(-1), n_samp).cpu().numpy().astype(np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -447,7 +496,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the configuration 3 / 5 legs (extra keys of the JSON line)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave the all-gather-v of the compressed blobs out of the step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # A multi-rank run that stops making progress (a rank that fell out of a collective) must end with every thread's
     # stack and a non-zero exit, not with the driver's kill: on by default when WORLD_SIZE > 1 (FA_BENCH_WATCHDOG_S
@@ -580,6 +633,8 @@ def main():
     # correctness of what was timed (outside the timed region)
     assert torch.equal(y, x), "decode(encode(x)) != x"
     c_bytes = comp.numel() / x.numel()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, comp, st, nb, y, n_samp)
 
     # the decode leg again with the frame CRC-16 check libFLAC performs (decompress.c:104-121): K9 beside K7 on a side
     # stream (event pair 4 closes after both), and the unverified decode timed the same way right beside it
