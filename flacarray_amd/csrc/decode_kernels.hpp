@@ -95,7 +95,12 @@ __global__ __launch_bounds__(256) void parse_streams_kernel(const uint8_t* __res
     if (ok && m.B > 0) {
         m.first_frame = starts[s] + off;
         const int64_t nf = (stream_size + m.B - 1) / m.B;
-        if (m.seek_abs >= 0 && m.npoints == nf) m.flags = 1;
+        // a table of nf points is complete only if its last point is the last frame's: placeholder points (sample
+        // number 0xFFFFFFFFFFFFFFFF, which libFLAC sorts to the end of a table) fill the table of a stream that
+        // has fewer real points; nf distinct frame starts end at frame nf - 1
+        if (m.seek_abs >= 0 && m.npoints == nf && nf > 0 &&
+            load_be64(p + (m.seek_abs - st0) + 18 * (nf - 1)) == (uint64_t)(nf - 1) * (uint64_t)m.B)
+            m.flags = 1;
         if (!(m.flags & 1)) {
             atomicAdd(err + 2, 1);
             const int64_t span = (nb - off + kScanSpan - 1) / kScanSpan + 1;
@@ -964,6 +969,12 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             ps = bs >> po;
             if (method > 1 || (po > 0 && (ps << po) != bs) || ps < order) bad = true;
             pleft = -order;  // partition 0 is short by `order`
+            if (!bad && ps == order) {
+                // partition 0 holds no residual (legal; libFLAC's decoder takes it): its parameter -- and an escape's
+                // width -- is stepped over here, so the first sample opens partition 1
+                if ((int)FA_GET(plen) == esc) (void)FA_GET(5);
+                pleft = 0;
+            }
         }
         if (bad) { mode = 3; task_live = false; atomicOr(a.err, kErrDecodeProcess); }
         if (mode != 3) {

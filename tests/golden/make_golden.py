@@ -16,21 +16,32 @@ import os
 import numpy as np
 
 
+def _crc_table(poly, width):
+    top, mask = 1 << (width - 1), (1 << width) - 1
+    tab = []
+    for i in range(256):
+        c = i << (width - 8)
+        for _ in range(8):
+            c = ((c << 1) ^ poly) & mask if c & top else (c << 1) & mask
+        tab.append(c)
+    return tab
+
+
+_CRC8 = _crc_table(0x07, 8)
+_CRC16 = _crc_table(0x8005, 16)
+
+
 def crc8(data):
     c = 0
     for b in data:
-        c ^= b
-        for _ in range(8):
-            c = ((c << 1) ^ 0x07) & 0xFF if c & 0x80 else (c << 1) & 0xFF
+        c = _CRC8[c ^ b]
     return c
 
 
 def crc16(data):
     c = 0
     for b in data:
-        c ^= b << 8
-        for _ in range(8):
-            c = ((c << 1) ^ 0x8005) & 0xFFFF if c & 0x8000 else (c << 1) & 0xFFFF
+        c = ((c << 8) & 0xFFFF) ^ _CRC16[(c >> 8) ^ b]
     return c
 
 
@@ -82,7 +93,7 @@ def residual(res, order, porder, params, bs, rice2=False, escapes=None):
             w = par[1]
             out += "1" * plen + ubits(w, 5)
             for _ in range(n):
-                assert -(1 << (w - 1)) <= res[i] < (1 << (w - 1)), "escape width too small"
+                assert (res[i] == 0) if w == 0 else (-(1 << (w - 1)) <= res[i] < (1 << (w - 1))), "escape width too small"
                 out += sbits(res[i], w)
                 i += 1
         else:
@@ -128,31 +139,39 @@ def subframe_bits(samples, bps, sub):
     return body
 
 
-def frame(samples, frame_no, bps, sub, ss_code=None, force_bs_code=None, assignment=0):
+def frame(samples, frame_no, bps, sub, ss_code=None, force_bs_code=None, assignment=0, sr_code=9, sr_value=0, blocking=0):
     """One frame.  Mono: `samples` is the channel and `sub` its description.  Two channels
     (assignment 1 left/right, 8 left/side, 9 side/right, 10 mid/side): `samples` is the pair of
     CODED channels (the caller has already formed side / mid) and `sub` the pair of descriptions;
-    a side channel is coded with one extra bit per sample."""
+    a side channel is coded with one extra bit per sample.  sr_code 12-14 append `sr_value` to the header (8 bits
+    for code 12, 16 for 13 / 14); blocking=1 sets the variable-blocksize bit (`frame_no` is then a sample number)."""
     chans = [samples] if assignment == 0 else list(samples)
     subs = [sub] if assignment == 0 else list(sub)
     bs = len(chans[0])
     code = force_bs_code if force_bs_code is not None else BS_CODES.get(bs, 6 if bs <= 256 else 7)
-    hdr = "11111111111110" + "0" + "0" + ubits(code, 4) + ubits(9, 4) + ubits(assignment, 4) + ubits(SS_CODES[bps] if ss_code is None else ss_code, 3) + "0"
+    hdr = "11111111111110" + "0" + ubits(blocking, 1) + ubits(code, 4) + ubits(sr_code, 4) + ubits(assignment, 4) + ubits(SS_CODES[bps] if ss_code is None else ss_code, 3) + "0"
     hdr += utf8(frame_no)
     if code == 6:
         hdr += ubits(bs - 1, 8)
     elif code == 7:
         hdr += ubits(bs - 1, 16)
+    if sr_code == 12:
+        hdr += ubits(sr_value, 8)
+    elif sr_code in (13, 14):
+        hdr += ubits(sr_value, 16)
     hdr += ubits(crc8(to_bytes(hdr)), 8)
     extra = {0: [0], 1: [0, 0], 8: [0, 1], 9: [1, 0], 10: [0, 1]}[assignment]
-    bits = hdr + "".join(subframe_bits(c, bps + e, sb) for c, e, sb in zip(chans, extra, subs))
+    # a description with "bits" is a subframe assembled by the caller
+    bits = hdr + "".join(sb["bits"] if "bits" in sb else subframe_bits(c, bps + e, sb) for c, e, sb in zip(chans, extra, subs))
     bits += "0" * ((-len(bits)) % 8)
     raw = to_bytes(bits)
     return raw + crc16(raw).to_bytes(2, "big")
 
 
-def stream(frames_bytes, blocksize, bps, total, extra_blocks=(), channels=1):
-    si = ubits(blocksize, 16) * 2 + ubits(0, 24) * 2 + ubits(44100, 20) + ubits(channels - 1, 3) + ubits(bps - 1, 5) + ubits(total, 36) + "0" * 128
+def stream(frames_bytes, blocksize, bps, total, extra_blocks=(), channels=1, frame_sizes=(0, 0), md5=bytes(16)):
+    """fLaC, STREAMINFO (min / max frame size and MD5 as given; zero = unknown), `extra_blocks` [(type, payload)], frames."""
+    si = (ubits(blocksize, 16) * 2 + ubits(frame_sizes[0], 24) + ubits(frame_sizes[1], 24) + ubits(44100, 20) + ubits(channels - 1, 3)
+          + ubits(bps - 1, 5) + ubits(total, 36) + "".join(ubits(b, 8) for b in md5))
     blocks = [(0, to_bytes(si))] + list(extra_blocks)
     out = b"fLaC"
     for i, (typ, payload) in enumerate(blocks):

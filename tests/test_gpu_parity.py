@@ -1482,3 +1482,54 @@ def test_side_channel_that_outgrows_32_bits_under_an_lpc_predictor(fa):
         assert np.array_equal(got.cpu().numpy()[0], want), sub["type"]
         part = fa.decode_flac_device(blob, st, nb, n, 30, 50, is_int64=True)
         assert np.array_equal(part.cpu().numpy()[0], want[30:50]), sub["type"]
+
+
+def test_first_partition_without_residuals(fa, oracle):
+    """A partition order whose first partition holds exactly `order` samples -- no residual, only its Rice parameter or
+    escape header -- is legal (libFLAC's decoder and the oracle take it; tests/golden/flac_writer.py writes it).  The
+    throughput decoder used to decode the frame's first residual with that empty partition's parameter."""
+    import torch
+
+    from tests.golden.make_golden import frame, stream
+
+    rng = np.random.default_rng(17)
+    n, block = 16 * 5 + 8, 16
+    x = np.cumsum(rng.integers(-3000, 3000, n)).astype(np.int64).tolist()
+    subs = [{"type": "fixed", "order": 2, "porder": 3, "params": [9, 14, 14, 14, 14, 14, 14, 14]},
+            {"type": "fixed", "order": 2, "porder": 3, "params": [("esc", 0), 14, 13, 14, 14, 14, 14, 14], "rice2": True},
+            {"type": "lpc", "order": 4, "coefs": [3, -3, 1, 0], "shift": 0, "precision": 4, "porder": 2,
+             "params": [("esc", 7)] + [20] * 3, "rice2": True},
+            {"type": "fixed", "order": 1, "porder": 4, "params": [0] + [14] * 15},
+            {"type": "fixed", "order": 2, "porder": 0, "params": [14]},
+            {"type": "fixed", "order": 4, "porder": 1, "params": [3, 14]}]
+    frs = [frame(x[f * block : (f + 1) * block], f, 32, subs[f]) for f in range(6)]
+    data = np.frombuffer(stream(frs, block, 32, n), dtype=np.uint8)
+    blob = np.concatenate([data, data])
+    st, nb = np.array([0, data.size], np.int64), np.full(2, data.size, np.int64)
+    want = np.array([x, x], dtype=np.int32)
+    assert np.array_equal(oracle.decode_i32(blob, st, nb, n), want)
+    d = [torch.from_numpy(a).cuda() for a in (blob, st, nb)]
+    assert np.array_equal(fa.decode_flac_device(*d, n).cpu().numpy(), want)
+    assert np.array_equal(fa.decode_flac_device(*d, n, 17, 70).cpu().numpy(), want[:, 17:70])
+    assert np.array_equal(fa.decode_flac(blob, st, nb, n), want)
+
+
+def test_seektable_padded_with_placeholder_points(fa, oracle):
+    """A SEEKTABLE with as many points as frames, the last of them placeholders (sample number 0xFFFFFFFFFFFFFFFF,
+    sorted to the end as libFLAC does) is not a complete table: the frames are found by the scan, not refused."""
+    import torch
+
+    n = 4096 * 5 + 99
+    x = sinusoid_noise_i32(3, n, seed=71)
+    blob, st, nb = oracle.encode_i32(x, 5)
+    hb = 4 + 4 + 34 + 4  # fLaC, STREAMINFO, SEEKTABLE header: the points follow
+    for s, keep in zip(st, (0, 2, 5)):
+        for f in range(keep, 6):
+            p = int(s) + hb + 18 * f
+            blob[p : p + 8] = 0xFF
+            blob[p + 8 : p + 18] = 0
+    assert np.array_equal(oracle.decode_i32(blob, st, nb, n), x)
+    d = [torch.from_numpy(a).cuda() for a in (blob, st, nb)]
+    assert np.array_equal(fa.decode_flac_device(*d, n).cpu().numpy(), x)
+    assert np.array_equal(fa.decode_flac_device(*d, n, 4095, 12300).cpu().numpy(), x[:, 4095:12300])
+    assert np.array_equal(fa.decode_flac(blob, st, nb, n), x)
