@@ -17,8 +17,11 @@ from .libflacarray import (
     encode_flac,
     encode_flac_device,
     encode_flac_device_f32,
+    encode_flac_device_f64,
     float32_to_int32_device,
+    float64_to_int64_device,
     set_decode_verify,
+    std_device,
 )
 from .utils import float_to_int, int_to_float, keep_select
 
@@ -39,9 +42,12 @@ __all__ = [
     "decode_flac",
     "encode_flac_device",
     "encode_flac_device_f32",
+    "encode_flac_device_f64",
     "decode_flac_device",
     "decode_slices_device",
     "float32_to_int32_device",
+    "float64_to_int64_device",
+    "std_device",
     "set_decode_verify",
     "float_to_int",
     "int_to_float",

@@ -43,6 +43,8 @@ SYMBOLS = [
     "fa_decode_slices_i64_device",
     "fa_float32_to_int32_device",
     "fa_int32_to_float32_device",
+    "fa_stream_std_f32_device",
+    "fa_stream_std_f64_device",
     "fa_decode_index_create",
     "fa_decode_index_destroy",
     "fa_decode_indexed",
@@ -63,7 +65,7 @@ SYMBOLS = [
     "fa_abi_version",
 ]
 
-ABI_VERSION = 2  # FA_ABI_VERSION of include/flacarray_hip.h this binding was written against
+ABI_VERSION = 3  # FA_ABI_VERSION of include/flacarray_hip.h this binding was written against
 
 # error bits (flacarray.h:20-40 + this library's additions)
 ERROR_DEVICE = 1 << 24
@@ -140,6 +142,10 @@ def lib():
     L.fa_float32_to_int32_device.restype = cint
     L.fa_int32_to_float32_device.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     L.fa_int32_to_float32_device.restype = cint
+    L.fa_stream_std_f32_device.argtypes = [vp, i64, i64, i64, vp, vp]
+    L.fa_stream_std_f32_device.restype = cint
+    L.fa_stream_std_f64_device.argtypes = [vp, i64, i64, i64, vp, vp]
+    L.fa_stream_std_f64_device.restype = cint
     L.fa_decode_index_create.argtypes = [vp, i64, vp, vp, i64, i64, cint, ctypes.POINTER(vp), vp]
     L.fa_decode_index_create.restype = cint
     L.fa_decode_index_destroy.argtypes = [vp]

@@ -368,22 +368,33 @@ class FlacArray:
         return [flat[o : o + c] for o, c in zip(out_off, count)]
 
     @classmethod
-    def from_device_array(cls, data, level=5, quanta=None):
-        """Construct a RESIDENT FlacArray from a torch tensor that already lives in HBM (int32 / int64, or
-        float32 with per-stream `quanta`): quantise + encode on the device, keep the store there, and mirror
-        it to host arrays so that every property of the reference API still answers with numpy."""
+    def from_device_array(cls, data, level=5, quanta=None, precision=None):
+        """Construct a RESIDENT FlacArray from a torch tensor that already lives in HBM (int32 / int64, or float32 /
+        float64 with `quanta` or `precision` as array_compress takes them): quantise + encode on the device, keep the
+        store there, and mirror it to host arrays so that every property of the reference API still answers with numpy.
+        Same store as from_array on the tensor's host copy; with `precision` the per-stream std is computed on the
+        device (std_device) and only its n_stream values reach the host.  Integer tensors ignore quanta / precision."""
         import torch
 
-        from .libflacarray import encode_flac_device, encode_flac_device_f32
+        from .compress import _per_stream_quanta
+        from .libflacarray import encode_flac_device, encode_flac_device_f32, encode_flac_device_f64
+        from .utils import stream_quanta
 
         offsets = gains = None
-        if data.dtype == torch.float32:
-            if quanta is None:
-                raise RuntimeError("Compressing floating point data ('float32') requires specifying either quanta or precision.")
-            lead = tuple(data.shape[:-1]) if data.dim() > 1 else (1,)
-            q = torch.as_tensor(quanta, dtype=torch.float32, device=data.device)
-            q = q.expand(lead).contiguous() if q.dim() == 0 else q
-            comp, st, nb, offsets, gains = encode_flac_device_f32(data.contiguous(), q, level=level, compact=True)
+        if data.dtype in (torch.float32, torch.float64):
+            ndt = np.dtype(np.float32) if data.dtype == torch.float32 else np.dtype(np.float64)
+            if quanta is None and precision is None:
+                raise RuntimeError(f"Compressing floating point data ('{ndt}') requires specifying either quanta or precision.")
+            if quanta is not None and precision is not None:
+                raise RuntimeError("Cannot set both quanta and precision")
+            encode = encode_flac_device_f32 if data.dtype == torch.float32 else encode_flac_device_f64
+            q = None
+            if quanta is not None:  # array_compress's checks and casts, on the host
+                if isinstance(quanta, torch.Tensor):
+                    quanta = quanta.item() if quanta.dim() == 0 else quanta.cpu().numpy()
+                lead = tuple(data.shape[:-1])
+                q = torch.from_numpy(stream_quanta(_per_stream_quanta(quanta, lead, ndt), lead, ndt)).to(data.device)
+            comp, st, nb, offsets, gains = encode(data.contiguous(), q, level=level, compact=True, precision=precision)
         elif data.dtype in (torch.int32, torch.int64):
             comp, st, nb = encode_flac_device(data.contiguous(), level=level, compact=True)
         else:

@@ -36,6 +36,7 @@
 #include "decode_latency.hpp"
 #include "quantize_kernels.hpp"
 #include "verify_kernels.hpp"
+#include "std_kernels.hpp"
 
 namespace {
 
@@ -59,8 +60,9 @@ struct DeviceState {
     std::map<int, float*> windows;  // blocksize -> device tukey(0.5) table
     uint16_t* crc_tab = nullptr;
     uint16_t* crc_tab_fused = nullptr;
-    void* scratch[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [10]: K1a partial ranges
-    size_t scratch_bytes[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // [10]: K1a partial ranges; [12]: std chunk sums and means, [13]: std summation plans (fa_stream_std_*_device)
+    void* scratch[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t scratch_epoch = 1;  // bumped whenever a scratch slot is (re)allocated or released: cached contents are then stale
     // frame-header table of the most recent encode geometry (host copy + what the device copy was built from)
     std::vector<uint4> h_hdr;
@@ -69,6 +71,9 @@ struct DeviceState {
     void* c_dp = nullptr;
     uint64_t c_epoch = 0;
     bool stamps_zeroed = false;
+    // (stream_size, chunk) whose summation plans scratch[13] holds, valid while scratch_epoch == std_plan_epoch
+    int64_t std_plan_key[2] = {-1, -1};
+    uint64_t std_plan_epoch = 0;
     hipStream_t feed_stream = nullptr;  // the host entry points' upload stream (created once: a new stream costs tens of ms)
     // small reads that want their samples on the host: the latency decoder stores them (and its status word) straight
     // into this pinned, device-visible buffer -- no copy calls, one stream synchronisation (decode_device_impl)
@@ -871,6 +876,84 @@ int validate_range(int64_t stream_size, int64_t first_sample, int64_t last_sampl
     return FA_ERROR_NONE;
 }
 
+
+// numpy's pairwise-sum tree of one chunk of `length` elements (flacarray_amd/npsum.py pairwise_plan): leaves (offset,
+// length) in element order and the postfix combine program (1 = push the next leaf's sum, 0 = add the top two)
+void std_build_plan(int64_t length, std::vector<int32_t>& leaves, std::vector<uint8_t>& ops) {
+    struct Node { int64_t off, n; bool done; };
+    std::vector<Node> stack{{0, length, false}};
+    while (!stack.empty()) {
+        const Node nd = stack.back();
+        stack.pop_back();
+        if (nd.n <= kStdLeaf) {
+            leaves.push_back((int32_t)nd.off);
+            leaves.push_back((int32_t)nd.n);
+            ops.push_back(1);
+        } else if (nd.done) {
+            ops.push_back(0);
+        } else {
+            int64_t n2 = nd.n / 2;
+            n2 -= n2 % 8;
+            stack.push_back({nd.off, nd.n, true});
+            stack.push_back({nd.off + n2, nd.n - n2, false});
+            stack.push_back({nd.off, n2, false});
+        }
+    }
+}
+
+// fa_stream_std_f32_device / _f64_device: S1 + S2 for the sum (-> means), S1 + S2 for the squared deviations (-> std)
+template <typename T>
+int stream_std_impl(const T* d_in, int64_t n_stream, int64_t stream_size, int64_t chunk, T* d_out, void* stream) {
+    FA_API_LOCK;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    if (chunk <= 0 || chunk > INT32_MAX || stream_size > INT64_MAX / 2) return FA_ERROR_CONVERT_TYPE;
+    const int64_t cps = (stream_size + chunk - 1) / chunk;
+    if (n_stream > INT32_MAX / cps) return FA_ERROR_CONVERT_TYPE;  // one workgroup per chunk: the grid's bound
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t tail = stream_size - (cps - 1) * chunk;
+    // plans of the chunk lengths the lane-per-leaf path does not cover
+    std::vector<int32_t> lv[2];
+    std::vector<uint8_t> op[2];
+    if (chunk != kStdFastChunk && stream_size >= chunk) std_build_plan(chunk, lv[0], op[0]);
+    if (tail != chunk && tail != kStdFastChunk) std_build_plan(tail, lv[1], op[1]);
+    const size_t lv_b = 4 * (lv[0].size() + lv[1].size());
+    const size_t plan_b = lv_b + op[0].size() + op[1].size();
+    const size_t sums_b = ((size_t)(n_stream * cps) * sizeof(T) + 255) & ~(size_t)255;
+    void *w = nullptr, *pl = nullptr;
+    int rc = get_scratch(12, sums_b + (size_t)n_stream * sizeof(T), &w);
+    if (rc) return rc;
+    if (plan_b && (rc = get_scratch(13, plan_b, &pl))) return rc;
+    if (plan_b && (ds_->std_plan_key[0] != stream_size || ds_->std_plan_key[1] != chunk || ds_->std_plan_epoch != ds_->scratch_epoch)) {
+        // a new geometry: upload its plans once (the copy is from pageable memory: wait before the vectors go)
+        std::vector<uint8_t> h(plan_b);
+        std::memcpy(h.data(), lv[0].data(), 4 * lv[0].size());
+        std::memcpy(h.data() + 4 * lv[0].size(), lv[1].data(), 4 * lv[1].size());
+        std::memcpy(h.data() + lv_b, op[0].data(), op[0].size());
+        std::memcpy(h.data() + lv_b + op[0].size(), op[1].data(), op[1].size());
+        FA_HIP_TRY(hipMemcpyAsync(pl, h.data(), plan_b, hipMemcpyHostToDevice, st));
+        FA_HIP_TRY(hipStreamSynchronize(st));
+        ds_->std_plan_key[0] = stream_size;
+        ds_->std_plan_key[1] = chunk;
+        ds_->std_plan_epoch = ds_->scratch_epoch;
+    }
+    const uint8_t* pb = reinterpret_cast<const uint8_t*>(pl);
+    StdPlanRef pf{reinterpret_cast<const int2*>(pb), pb + lv_b, (int)(lv[0].size() / 2), (int)op[0].size()};
+    StdPlanRef pt{reinterpret_cast<const int2*>(pb + 4 * lv[0].size()), pb + lv_b + op[0].size(), (int)(lv[1].size() / 2),
+                  (int)op[1].size()};
+    T* sums = reinterpret_cast<T*>(w);
+    T* means = reinterpret_cast<T*>(reinterpret_cast<uint8_t*>(w) + sums_b);
+    const unsigned grid = (unsigned)(n_stream * cps), fgrid = (unsigned)((n_stream + 255) / 256);
+    hipLaunchKernelGGL((stream_chunk_sum_kernel<T, false>), dim3(grid), dim3(64), 0, st, d_in, stream_size, chunk, cps,
+                       (const T*)nullptr, pf, pt, sums);
+    hipLaunchKernelGGL((stream_fold_kernel<T, false>), dim3(fgrid), dim3(256), 0, st, sums, n_stream, stream_size, cps, means);
+    hipLaunchKernelGGL((stream_chunk_sum_kernel<T, true>), dim3(grid), dim3(64), 0, st, d_in, stream_size, chunk, cps,
+                       (const T*)means, pf, pt, sums);
+    hipLaunchKernelGGL((stream_fold_kernel<T, true>), dim3(fgrid), dim3(256), 0, st, sums, n_stream, stream_size, cps, d_out);
+    FA_HIP_TRY(hipGetLastError());
+    return FA_ERROR_NONE;
+}
+
 }  // namespace
 
 extern "C" {
@@ -922,7 +1005,7 @@ int fa_device_count(void) {
 
 void fa_release_scratch(void) {
     FA_API_LOCK_OR(return);
-    for (int i = 0; i < 12; ++i) {
+    for (int i = 0; i < 14; ++i) {
         if (ds_->scratch[i]) (void)hipFree(ds_->scratch[i]);
         ds_->scratch[i] = nullptr;
         ds_->scratch_bytes[i] = 0;
@@ -1683,6 +1766,14 @@ int fa_int64_to_float64_device(const int64_t* d_input, int64_t n_stream, int64_t
                        d_offsets, d_gains, d_output);
     FA_HIP_TRY(hipGetLastError());
     return FA_ERROR_NONE;
+}
+
+int fa_stream_std_f32_device(const float* d_in, int64_t n_stream, int64_t stream_size, int64_t chunk, float* d_out, void* stream) {
+    return stream_std_impl<float>(d_in, n_stream, stream_size, chunk, d_out, stream);
+}
+
+int fa_stream_std_f64_device(const double* d_in, int64_t n_stream, int64_t stream_size, int64_t chunk, double* d_out, void* stream) {
+    return stream_std_impl<double>(d_in, n_stream, stream_size, chunk, d_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -614,7 +614,46 @@ def _verify_arg(verify):
     return -1 if verify is None else (1 if verify else 0)
 
 
-def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=False):
+def std_device(data):
+    """Per-stream standard deviation of a C-contiguous float32 / float64 CUDA tensor [..., stream_size], bit for bit
+    np.std(data.cpu().numpy(), axis=-1) (numpy's chunked pairwise summation, chunk = np.getbufsize() at call time;
+    flacarray_amd/npsum.py).  Returns a tensor of the data's dtype with the leading shape, (1,) for a 1-D tensor; it is
+    complete in stream order (no wait on the stream)."""
+    torch = _torch()
+    if data.dtype not in (torch.float32, torch.float64):
+        raise ValueError("Only float32 and float64 data are supported")
+    if not data.is_contiguous():
+        raise RuntimeError("Only C-contiguous arrays are supported")
+    if not data.is_cuda:
+        raise RuntimeError("std_device needs a tensor on the GPU")
+    if data.dim() == 0 or data.numel() == 0:
+        raise ValueError("std_device needs a non-empty array with a stream axis")
+    lead = tuple(data.shape[:-1]) if data.dim() > 1 else (1,)
+    n_stream = int(np.prod(lead))
+    out = torch.empty(n_stream, dtype=data.dtype, device=data.device)
+    L = _lib.lib()
+    fn = L.fa_stream_std_f32_device if data.dtype == torch.float32 else L.fa_stream_std_f64_device
+    with _on_device(data.device):
+        errcode = fn(_dp(data), n_stream, data.shape[-1], int(np.getbufsize()), _dp(out), _stream_ptr())
+    if errcode != 0:
+        raise RuntimeError(f"Standard deviation failed, return code = {errcode}")
+    return out.reshape(lead)
+
+
+def _precision_quanta_device(data, precision):
+    """Per-stream quanta rms / 10^p for device data as a tensor on its device: the std on the device, its n_stream
+    values copied to the host (the one wait), then the host path's own numpy expression (utils.precision_quanta)."""
+    from .utils import precision_quanta, stream_quanta
+
+    torch = _torch()
+    lead = tuple(data.shape[:-1])  # numpy's leading shape: () for a 1-D array
+    ndt = np.float32 if data.dtype == torch.float32 else np.float64
+    rms = std_device(data).cpu().numpy().reshape(lead)
+    q = stream_quanta(precision_quanta(rms, lead, precision), lead, ndt)
+    return torch.from_numpy(q).to(data.device)
+
+
+def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=False, precision=None):
     """Quantise and encode a C-contiguous float32 CUDA tensor [..., stream_size] held in HBM: the device-resident
     analogue of array_compress on float32 input (compress.py:50-84 -> float_to_int + encode_flac).
 
@@ -622,7 +661,8 @@ def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=F
     (compressed, starts, nbytes, offsets, gains), offsets / gains float32 with the leading shape of `data`.  Where
     the single-pass kernel applies (levels 3-8, stream length a multiple of 4096) the quantisation happens in the
     encoder's staging load after a range pre-pass -- the int32 array never exists in HBM; otherwise the two steps
-    run one after the other.  Same bytes, offsets and gains either way."""
+    run one after the other.  Same bytes, offsets and gains either way.  `precision` p (instead of `quanta`): quanta =
+    std / 10^p per stream as array_compress derives them (std_device, then the host path's numpy expression)."""
     torch = _torch()
     if data.dtype != torch.float32 or not data.is_contiguous():
         raise ValueError("Only float32 and float64 data are supported")
@@ -630,6 +670,10 @@ def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=F
         raise RuntimeError("encode_flac_device_f32 needs a tensor on the GPU")
     if level < 0 or level > 8:
         raise RuntimeError("FLAC only supports compression levels 0-8")
+    if precision is not None:
+        if quanta is not None:
+            raise RuntimeError("Cannot set both quanta and precision")
+        quanta = _precision_quanta_device(data, precision)
     stream_size = data.shape[-1]
     lead = tuple(data.shape[:-1]) if data.dim() > 1 else (1,)
     n_stream = int(np.prod(lead))
@@ -639,7 +683,8 @@ def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=F
         if q.numel() != n_stream:
             raise RuntimeError("quanta must have one entry per stream")
     L = _lib.lib()
-    if not (data.data_ptr() % 16 == 0 and stream_size % 4096 == 0 and L.fa_encode_single_pass_supported(n_stream, stream_size, level)):
+    # (the fused kernel, K3F, takes levels 3-8 only: levels 0-2 of any length quantise first, then go to K3G)
+    if not (level >= 3 and data.data_ptr() % 16 == 0 and stream_size % 4096 == 0 and L.fa_encode_single_pass_supported(n_stream, stream_size, level)):
         ints, offsets, gains = float32_to_int32_device(data, q)
         comp, st, nb = encode_flac_device(ints, level=level, workspace=workspace, compact=compact)
         return comp, st, nb, offsets, gains
@@ -666,6 +711,29 @@ def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=F
     if compact:
         compressed = compressed.clone()
     return compressed, starts.reshape(lead), nbytes.reshape(lead), offsets.reshape(lead), gains.reshape(lead)
+
+
+def encode_flac_device_f64(data, quanta=None, level=5, workspace=None, compact=False, precision=None):
+    """Quantise and encode a C-contiguous float64 CUDA tensor [..., stream_size] held in HBM: the device-resident
+    analogue of array_compress on float64 input (float64_to_int64, then the two-channel encoder).
+
+    `quanta`: None (per-stream quanta from the data range) or a tensor with one value per stream; `precision` p
+    instead: quanta = std / 10^p per stream, as for encode_flac_device_f32.  Returns (compressed, starts, nbytes,
+    offsets, gains), offsets / gains float64 with the leading shape of `data`."""
+    torch = _torch()
+    if data.dtype != torch.float64 or not data.is_contiguous():
+        raise ValueError("Only float32 and float64 data are supported")
+    if not data.is_cuda:
+        raise RuntimeError("encode_flac_device_f64 needs a tensor on the GPU")
+    if level < 0 or level > 8:
+        raise RuntimeError("FLAC only supports compression levels 0-8")
+    if precision is not None:
+        if quanta is not None:
+            raise RuntimeError("Cannot set both quanta and precision")
+        quanta = _precision_quanta_device(data, precision)
+    ints, offsets, gains = float64_to_int64_device(data, quanta)
+    comp, st, nb = encode_flac_device(ints, level=level, workspace=workspace, compact=compact)
+    return comp, st, nb, offsets, gains
 
 
 def _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, is_int64):
@@ -935,6 +1003,33 @@ def float32_to_int32_device(data, quanta=None):
             raise RuntimeError("quanta must have one entry per stream")
     with _on_device(data.device):
         errcode = _lib.lib().fa_float32_to_int32_device(
+            _dp(data), n_stream, stream_size, _dp(q), _dp(out), _dp(offsets), _dp(gains), _stream_ptr()
+        )
+    if errcode & _lib.ERROR_NAN_INPUT:
+        raise RuntimeError("Cannot convert data with NaNs to integers")
+    if errcode != 0:
+        raise RuntimeError(f"Encoding failed, return code = {errcode}")
+    return out, offsets.reshape(lead), gains.reshape(lead)
+
+
+def float64_to_int64_device(data, quanta=None):
+    """Device float64 -> int64 quantisation (utils.c:245-327); returns (int64 tensor, offsets, gains)."""
+    torch = _torch()
+    if data.dtype != torch.float64 or not data.is_contiguous():
+        raise ValueError("Only float32 and float64 data are supported")
+    stream_size = data.shape[-1]
+    lead = tuple(data.shape[:-1]) if data.dim() > 1 else (1,)
+    n_stream = int(np.prod(lead))
+    out = torch.empty(data.shape, dtype=torch.int64, device=data.device)
+    offsets = torch.empty(n_stream, dtype=torch.float64, device=data.device)
+    gains = torch.empty(n_stream, dtype=torch.float64, device=data.device)
+    q = None
+    if quanta is not None:
+        q = quanta.to(device=data.device, dtype=torch.float64).reshape(-1).contiguous()
+        if q.numel() != n_stream:
+            raise RuntimeError("quanta must have one entry per stream")
+    with _on_device(data.device):
+        errcode = _lib.lib().fa_float64_to_int64_device(
             _dp(data), n_stream, stream_size, _dp(q), _dp(out), _dp(offsets), _dp(gains), _stream_ptr()
         )
     if errcode & _lib.ERROR_NAN_INPUT:

@@ -69,19 +69,30 @@ def _per_stream(values, lead, what):
     return arr, None
 
 
-def _quanta_for(data, lead, quanta, precision):
-    """The quanta handed to the C layer: a zero-length array means "derive them from the data range"
-    (libflacarray.pyx:142-144); `precision` p stands for quanta = rms / 10^p per stream (utils.py:284-296)."""
-    if precision is not None:
-        rms = np.std(data, axis=-1, keepdims=True).reshape(lead)
-        p_arr, p_scalar = _per_stream(precision, lead, "precision")
-        quanta = rms / 10 ** (p_arr.reshape(lead) if p_arr is not None else p_scalar)
+def precision_quanta(rms, lead, precision):
+    """quanta = rms / 10^p per stream (utils.py:284-296): `rms` the per-stream std shaped like `lead`, `precision` a
+    scalar or an array of that shape.  The numpy expression itself, so its promotion rules hold wherever the std came
+    from (a scalar int p divides in the data dtype, an int array p in float64)."""
+    p_arr, p_scalar = _per_stream(precision, lead, "precision")
+    return rms / 10 ** (p_arr.reshape(lead) if p_arr is not None else p_scalar)
+
+
+def stream_quanta(quanta, lead, dtype):
+    """The quanta handed to the C layer, one per stream in `dtype`: a zero-length array means "derive them from the
+    data range" (libflacarray.pyx:142-144)."""
     if quanta is None:
-        return np.zeros(0, dtype=data.dtype)
+        return np.zeros(0, dtype=dtype)
     q_arr, q_scalar = _per_stream(quanta, lead, "quanta")
     if q_arr is None:
-        q_arr = np.full(lead, q_scalar, dtype=data.dtype)
-    return q_arr.reshape(-1).astype(data.dtype)
+        q_arr = np.full(lead, q_scalar, dtype=dtype)
+    return q_arr.reshape(-1).astype(dtype)
+
+
+def _quanta_for(data, lead, quanta, precision):
+    """The quanta handed to the C layer for host data; `precision` p stands for quanta = rms / 10^p per stream."""
+    if precision is not None:
+        quanta = precision_quanta(np.std(data, axis=-1, keepdims=True).reshape(lead), lead, precision)
+    return stream_quanta(quanta, lead, data.dtype)
 
 
 def float_to_int(data, quanta=None, precision=None):

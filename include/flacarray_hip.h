@@ -264,6 +264,17 @@ int fa_float64_to_int64_device(const double* d_input, int64_t n_stream, int64_t 
 int fa_int64_to_float64_device(const int64_t* d_input, int64_t n_stream, int64_t stream_size, const double* d_offsets,
                                const double* d_gains, double* d_output, void* stream);
 
+/* Per-stream standard deviation of d_in[n_stream][stream_size] (C-contiguous, device) into d_out[n_stream], bit for bit
+ * what numpy's np.std(x, axis=-1) gives for the contiguous host copy when np.getbufsize() == chunk: each row is summed
+ * in chunks of `chunk` elements (numpy's pairwise sum per chunk, chunk sums added in order), mean = T(double(sum) / n),
+ * then the same sum of T((x - mean)^2), var = T(double(sum) / n), std = sqrt(var) correctly rounded; a NaN gives NaN.
+ * Four launches in stream order, no wait on the stream -- except once when (stream_size, chunk) changes and the chunk
+ * needs a summation plan (any chunk length other than 8192; flacarray_amd/npsum.py pairwise_plan): the plan is uploaded.
+ * Workspace: the library's per-device scratch (n_stream * ceil(stream_size / chunk) + n_stream values), so calls of one
+ * device on different streams must not overlap.  FA_ERROR_CONVERT_TYPE for chunk <= 0 or more than 2^31 - 1 chunks. */
+int fa_stream_std_f32_device(const float* d_in, int64_t n_stream, int64_t stream_size, int64_t chunk, float* d_out, void* stream);
+int fa_stream_std_f64_device(const double* d_in, int64_t n_stream, int64_t stream_size, int64_t chunk, double* d_out, void* stream);
+
 /* Kernel timing for bench.py: when enabled, HIP events are recorded on the launch stream around
  * the three dominant kernels of the most recent calls; fa_profile_last waits for them and
  * returns milliseconds {encode_frames_kernel, compact_frames_kernel, decode_frames_kernel<8>}
@@ -286,10 +297,10 @@ const char* fa_version(void);
 
 /* ABI revision of the group-2 (fa_*) signatures in this header.  It is raised whenever an existing entry point changes
  * its argument list (revision 2: the trailing `int verify` of the device decode entry points, 1 / 0 / negative = check /
- * do not / process default, see fa_set_decode_verify); a binding built against
+ * do not / process default, see fa_set_decode_verify; revision 3 added the std entry points); a binding built against
  * another revision must refuse the library instead of calling it with a shifted argument list --
  * flacarray_amd/_lib.py does. */
-#define FA_ABI_VERSION 2  /* (new entry points do not raise it: fa_encode_f64_host came with revision 2) */
+#define FA_ABI_VERSION 3  /* (revision 3: fa_stream_std_f32_device / fa_stream_std_f64_device) */
 int fa_abi_version(void);
 
 #ifdef __cplusplus
