@@ -11,6 +11,7 @@ from .compress import array_compress
 from .decompress import array_decompress, array_decompress_slice
 from .libflacarray import (
     DeviceDecodeIndex,
+    compare_flac_device,
     decode_flac,
     decode_flac_device,
     decode_slices_device,
@@ -21,6 +22,7 @@ from .libflacarray import (
     float32_to_int32_device,
     float64_to_int64_device,
     set_decode_verify,
+    set_encode_verify,
     std_device,
 )
 from .utils import float_to_int, int_to_float, keep_select
@@ -45,10 +47,12 @@ __all__ = [
     "encode_flac_device_f64",
     "decode_flac_device",
     "decode_slices_device",
+    "compare_flac_device",
     "float32_to_int32_device",
     "float64_to_int64_device",
     "std_device",
     "set_decode_verify",
+    "set_encode_verify",
     "float_to_int",
     "int_to_float",
     "keep_select",

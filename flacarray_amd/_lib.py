@@ -49,6 +49,9 @@ SYMBOLS = [
     "fa_decode_index_destroy",
     "fa_decode_indexed",
     "fa_set_decode_verify",
+    "fa_set_encode_verify",
+    "fa_compare_i32_device",
+    "fa_compare_i64_device",
     "fa_encode_f32_host",
     "fa_encode_f64_host",
     "fa_decode_f32_host",
@@ -65,11 +68,12 @@ SYMBOLS = [
     "fa_abi_version",
 ]
 
-ABI_VERSION = 3  # FA_ABI_VERSION of include/flacarray_hip.h this binding was written against
+ABI_VERSION = 4  # FA_ABI_VERSION of include/flacarray_hip.h this binding was written against
 
 # error bits (flacarray.h:20-40 + this library's additions)
 ERROR_DEVICE = 1 << 24
 ERROR_NAN_INPUT = 1 << 25
+ERROR_ENCODE_VERIFY = 1 << 26
 
 _lib = None
 _libc = None
@@ -168,6 +172,11 @@ def lib():
     L.fa_pinned_free.restype = None
     L.fa_set_decode_verify.argtypes = [cint]
     L.fa_set_decode_verify.restype = cint
+    L.fa_set_encode_verify.argtypes = [cint]
+    L.fa_set_encode_verify.restype = cint
+    for name in ("fa_compare_i32_device", "fa_compare_i64_device"):
+        getattr(L, name).argtypes = [vp, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp]
+        getattr(L, name).restype = cint
     L.fa_profile_enable.argtypes = [cint]
     L.fa_profile_enable.restype = None
     L.fa_profile_last.argtypes = [ctypes.POINTER(ctypes.c_float)]

@@ -367,19 +367,57 @@ class FlacArray:
         count = np.asarray(count, dtype=np.int64)
         return [flat[o : o + c] for o, c in zip(out_off, count)]
 
+    def first_mismatch(self, data):
+        """Check the store against `data` (a numpy array or a torch tensor of this array's shape and dtype) without
+        decoding into memory: returns a numpy int64 array of the leading shape holding, per stream, the index of the
+        first sample whose decoded value differs from `data`, or -1 where the stream decodes to `data`.  Float stores
+        compare through their offsets and gains: what is compared is the quantised integers, not the floats, so a float
+        change that leaves its quantised integer the same is not a mismatch.  Uses the resident store after to_device(),
+        and uploads the store otherwise."""
+        import torch
+
+        from .libflacarray import compare_flac_device
+
+        shape = tuple(int(n) for n in data.shape)
+        if shape != tuple(self._shape):
+            raise ValueError(f"data of shape {shape} does not match the array's shape {tuple(self._shape)}")
+        dt = np.dtype(str(data.dtype).replace("torch.", "")) if isinstance(data, torch.Tensor) else data.dtype
+        if dt != self._dtype:
+            raise ValueError(f"data of dtype {dt} does not match the array's dtype {self._dtype}")
+        res = self._resident
+        if res is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(-1)).to(dev)  # noqa: E731
+            ft = np.float64 if self._is_int64 else np.float32
+            comp, st, nb = up(self._compressed, np.uint8), up(self._stream_starts, np.int64), up(self._stream_nbytes, np.int64)
+            off, gain = up(self._stream_offsets, ft), up(self._stream_gains, ft)
+        else:
+            dev = res["device"]
+            comp, st, nb, off, gain = res["compressed"], res["starts"], res["nbytes"], res["offsets"], res["gains"]
+        if isinstance(data, torch.Tensor):
+            x = data.to(dev).contiguous()
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+        first = compare_flac_device(comp, st, nb, x.reshape(self._st.count, self._stream_size), off, gain)
+        return first.cpu().numpy().reshape(self._leading_shape)
+
     @classmethod
-    def from_device_array(cls, data, level=5, quanta=None, precision=None):
+    def from_device_array(cls, data, level=5, quanta=None, precision=None, verify=None):
         """Construct a RESIDENT FlacArray from a torch tensor that already lives in HBM (int32 / int64, or float32 /
         float64 with `quanta` or `precision` as array_compress takes them): quantise + encode on the device, keep the
         store there, and mirror it to host arrays so that every property of the reference API still answers with numpy.
         Same store as from_array on the tensor's host copy; with `precision` the per-stream std is computed on the
-        device (std_device) and only its n_stream values reach the host.  Integer tensors ignore quanta / precision."""
+        device (std_device) and only its n_stream values reach the host.  Integer tensors ignore quanta / precision.
+        `verify`: compare the store with `data` on the device before returning (see array_compress); None = the default
+        of set_encode_verify."""
         import torch
 
         from .compress import _per_stream_quanta
-        from .libflacarray import encode_flac_device, encode_flac_device_f32, encode_flac_device_f64
+        from .libflacarray import _encode_verify_default, encode_flac_device, encode_flac_device_f32, encode_flac_device_f64
         from .utils import stream_quanta
 
+        if verify is None:
+            verify = _encode_verify_default()
         offsets = gains = None
         if data.dtype in (torch.float32, torch.float64):
             ndt = np.dtype(np.float32) if data.dtype == torch.float32 else np.dtype(np.float64)
@@ -394,9 +432,9 @@ class FlacArray:
                     quanta = quanta.item() if quanta.dim() == 0 else quanta.cpu().numpy()
                 lead = tuple(data.shape[:-1])
                 q = torch.from_numpy(stream_quanta(_per_stream_quanta(quanta, lead, ndt), lead, ndt)).to(data.device)
-            comp, st, nb, offsets, gains = encode(data.contiguous(), q, level=level, compact=True, precision=precision)
+            comp, st, nb, offsets, gains = encode(data.contiguous(), q, level=level, compact=True, precision=precision, verify=verify)
         elif data.dtype in (torch.int32, torch.int64):
-            comp, st, nb = encode_flac_device(data.contiguous(), level=level, compact=True)
+            comp, st, nb = encode_flac_device(data.contiguous(), level=level, compact=True, verify=verify)
         else:
             raise ValueError(f"Unsupported data type '{data.dtype}'")
         host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
@@ -409,11 +447,11 @@ class FlacArray:
         return out
 
     @classmethod
-    def from_array(cls, arr, level=5, quanta=None, precision=None, mpi_comm=None, use_threads=False):
-        """Construct a FlacArray from a numpy ndarray (array.py:587-637)."""
+    def from_array(cls, arr, level=5, quanta=None, precision=None, mpi_comm=None, use_threads=False, verify=None):
+        """Construct a FlacArray from a numpy ndarray (array.py:587-637).  `verify`: see array_compress."""
         if mpi_comm is not None:
             raise NotImplementedError("mpi4py communicators are not supported; see flacarray_amd.dist")
-        pieces = array_compress(arr, level=level, quanta=quanta, precision=precision, use_threads=use_threads)
+        pieces = array_compress(arr, level=level, quanta=quanta, precision=precision, use_threads=use_threads, verify=verify)
         return cls._assemble(arr.shape, None, arr.dtype, *pieces)
 
     @classmethod

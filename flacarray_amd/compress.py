@@ -6,7 +6,7 @@ encoder's load for float32, in front of the two-channel encoder for float64) -- 
 """
 import numpy as np
 
-from .libflacarray import encode_flac, encode_flac_f32, encode_flac_f64
+from .libflacarray import _EncodeVerify, encode_flac, encode_flac_f32, encode_flac_f64
 from .utils import _quanta_for, _streams_of, function_timer
 
 _INT_KINDS = (np.dtype(np.int32), np.dtype(np.int64))
@@ -29,7 +29,7 @@ def _per_stream_quanta(quanta, leading_shape, dtype):
 
 
 @function_timer
-def array_compress(arr, level=5, quanta=None, precision=None, use_threads=False):
+def array_compress(arr, level=5, quanta=None, precision=None, use_threads=False, verify=None):
     """Compress a numpy array with optional floating point conversion.
 
     Integer input (int32, int64) is compressed as is and the last two elements of the result are None.
@@ -38,9 +38,18 @@ def array_compress(arr, level=5, quanta=None, precision=None, use_threads=False)
 
     Returns (compressed bytes, stream starts, stream nbytes, stream offsets, stream gains); the
     auxiliary arrays have the leading shape of `arr` (one element for a single stream).
+
+    `verify`: True = decode the streams on the device right after they are written and compare them with the input
+    before returning (libFLAC's verify mode: RuntimeError on a difference; float input compares as the quantised
+    integers, not the floats), False = do not, None = the default of set_encode_verify.
     """
     if arr.size == 0:
         raise ValueError("Cannot compress a zero-sized array!")
+    with _EncodeVerify(verify):
+        return _compress(arr, level, quanta, precision, use_threads)
+
+
+def _compress(arr, level, quanta, precision, use_threads):
     kind = arr.dtype
 
     if kind in _INT_KINDS:

@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "flac_math.hpp"
+#include "quantize_kernels.hpp"
 
 namespace fa {
 
@@ -510,6 +511,12 @@ struct DecodeArgs {
     int32_t* assign;    // [n_tasks] channel assignment once both subframes are decoded, else -1
     int32_t hib_words;  // ceil(B / 32)
     int32_t verbatim_done;  // NCH == 2: VERBATIM first subframes (no wasted bits) were decoded by verbatim_channel0_kernel
+    // compare sink (decode_frames_kernel<..., CMP = true>, compare_channels_kernel; grid mode over whole streams): the
+    // caller's samples stand where the output would be -- int32 / int64, or float32 / float64 quantised with `offsets` /
+    // `gains` first -- and first_mismatch[stream] receives the smallest sample index that differs (atomicMin; all ones,
+    // i.e. -1 as int64, where nothing differs)
+    const void* cmp;
+    unsigned long long* first_mismatch;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -755,7 +762,13 @@ __device__ __noinline__ BitsRet slow_sample(const uint8_t* cbase, const uint8_t*
 // decodes its frame's two subframes one after the other into a task-local planar image
 // tmp[(task * 2 + channel) * B + sample] (low 32 bits) plus one bit per sample for bit 32 (side
 // channels carry 33 bits); combine_channels_kernel undoes the stereo decorrelation and writes int64.
-template <int MO, int MO_DONE, bool F32, int NCH>
+// CMP (grid mode over whole streams): a frame the decoder rejects lowers a.first_mismatch[stream] to the frame's first
+// sample instead of setting the error word.  With one channel the tile store becomes the compare sink: where the store
+// would write a piece of a tile row, the same 16 bytes of the caller's input (a.cmp) are loaded in the same pattern --
+// float32 input quantised with the row's offset and gain (quantise_f32, the encoder's own arithmetic) -- and compared
+// with the decoded integers; a lane that finds a difference lowers a.first_mismatch[stream] to its first differing
+// sample.  Matching data issue no atomics.  Two channels keep the planar image, which compare_channels_kernel compares.
+template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false>
 #ifndef FA_K7_WAVES_ATTR
 #define FA_K7_WAVES_ATTR
 #endif
@@ -766,6 +779,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     constexpr int kTileG = kTileW / 4;
     constexpr int kTileSwz = 32 / kTileG;
     static_assert(NCH == 1 || (kTileW == 32 && !F32), "two-channel variant: 32-sample tiles, integer output");
+    constexpr bool SINK = CMP && NCH == 1;  // the tile store compares instead of writing
     // one LDS object, so that the ring image starts at LDS address 0 (ring_words builds its addresses with an OR)
     __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + kTileW * kLaneStride + (F32 ? 128 : 0)];
     uint32_t* const rings = lds_k7;
@@ -795,6 +809,11 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         }
     }
     const int64_t fstart = f * (int64_t)a.B;
+    // a frame the decoder rejects: the error word, or (compare sink) a mismatch at the frame's first sample
+    auto reject = [&]() __attribute__((always_inline)) {
+        if constexpr (CMP) atomicMin(a.first_mismatch + s, (unsigned long long)fstart);
+        else atomicOr(a.err, kErrDecodeProcess);
+    };
     // reader state
     const uint8_t* cbase = a.blob;
     const uint8_t* const lim16 = reinterpret_cast<const uint8_t*>((reinterpret_cast<uintptr_t>(a.blob + a.blob_bytes) + 15) & ~(uintptr_t)15);
@@ -866,9 +885,10 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         if constexpr (NCH == 2) {
             if (a.assign[task] >= 0) task_live = false;  // completed by an earlier (shallower) pass
         }
-        if (bad) { task_live = false; atomicOr(a.err, kErrDecodeProcess); }
+        if (bad) { task_live = false; reject(); }
     }
-    const bool out_aligned = ((reinterpret_cast<uintptr_t>(a.out_f32 ? (const void*)a.out_f32 : (const void*)a.out_i32) & 15) == 0);
+    const void* const out_base = SINK ? a.cmp : (a.out_f32 ? (const void*)a.out_f32 : (const void*)a.out_i32);
+    const bool out_aligned = ((reinterpret_cast<uintptr_t>(out_base) & 15) == 0);
 
     // read `n` (1..33) bits as a signed value; 33-bit values (side channels) only exist for NCH == 2
     auto get_wide = [&](int n) __attribute__((always_inline)) -> double {
@@ -976,7 +996,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                 pleft = 0;
             }
         }
-        if (bad) { mode = 3; task_live = false; atomicOr(a.err, kErrDecodeProcess); }
+        if (bad) { mode = 3; task_live = false; reject(); }
         if (mode != 3) {
             int64_t l = sl_first - fstart, h2 = sl_last - fstart;
             if (l < 0) l = 0;
@@ -1063,7 +1083,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         float og = 0.0f, cf = 1.0f;
         if (mode != 3) {
             og = a.offsets[s];
-            cf = (float)(1.0 / (double)a.gains[s]);  // utils.c:361
+            if constexpr (SINK) cf = a.gains[s];  // (quantise_f32 of the input)
+            else cf = (float)(1.0 / (double)a.gains[s]);  // utils.c:361
         }
         row_fg[lane] = make_float2(og, cf);
     }
@@ -1209,7 +1230,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                         nbp = sr.bitpos;
                         next_chunk = sr.next_chunk;
                         if (sr.bad) {  // stop consuming: the rest of this lane's frame is zero-width
-                            atomicOr(a.err, kErrDecodeProcess);
+                            reject();
                             escw = 0; zlim = 0u; pleft = 0x7fffffff; r = 0; nbp = bitpos;
                         }
                     }
@@ -1268,6 +1289,35 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         }
     };
 
+    // compare sink: the caller's samples at output element o (of row r), as the encoder's integers
+    auto input4 = [&](int64_t o, int r) __attribute__((always_inline)) -> int4 {
+        if constexpr (F32) {
+            const float4 x = *reinterpret_cast<const float4*>(static_cast<const float*>(a.cmp) + o);
+            const float2 fg = row_fg[r];
+            return make_int4(quantise_f32(x.x, fg.x, fg.y), quantise_f32(x.y, fg.x, fg.y), quantise_f32(x.z, fg.x, fg.y),
+                             quantise_f32(x.w, fg.x, fg.y));
+        } else {
+            return *reinterpret_cast<const int4*>(static_cast<const int32_t*>(a.cmp) + o);
+        }
+    };
+    auto input1 = [&](int64_t o, int r) __attribute__((always_inline)) -> int32_t {
+        if constexpr (F32) {
+            const float2 fg = row_fg[r];
+            return quantise_f32(static_cast<const float*>(a.cmp)[o], fg.x, fg.y);
+        } else {
+            return static_cast<const int32_t*>(a.cmp)[o];
+        }
+    };
+    // j = first differing column (0..3) of the piece of row r at output element o, 4 = none; every lane of the wave
+    // calls it (the stream of row r comes from its owner lane), only lanes with a difference issue the atomic
+    const int s32 = (int)s;
+    auto report = [&](int r, int64_t o, int j) __attribute__((always_inline)) {
+        if (__builtin_expect(__any(j < 4), 0)) {
+            const int rs = __builtin_amdgcn_ds_bpermute(r << 2, s32);
+            if (j < 4) atomicMin(a.first_mismatch + rs, (unsigned long long)(o + j - (int64_t)rs * a.stream_size));
+        }
+    };
+
     // cooperative store of the tile: (64 / kTileG) rows x kTileW samples per pass, 16 bytes per lane
     auto flush_tile = [&](int tbase) __attribute__((always_inline)) {
         __builtin_amdgcn_wave_barrier();
@@ -1277,7 +1327,43 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             hbw = 0;
         }
         constexpr int kRowsPerPass = 64 / kTileG;
-        if (all_al && tbase >= lo_max && tbase + kTileW <= hi_min) {
+        if constexpr (SINK) {
+            if (all_al && tbase >= lo_max && tbase + kTileW <= hi_min) {
+                // whole tile, aligned rows: every piece's input is requested first and compared after, so that the loads
+                // overlap one another and the tile's LDS reads; one wave-uniform test decides whether anything is reported
+                int4 x[kTileG];
+#pragma unroll
+                for (int it = 0; it < kTileG; ++it)
+                    x[it] = *reinterpret_cast<const int4*>(static_cast<const int32_t*>(a.cmp) + rout[it] + tbase + 4 * (lane % kTileG));
+                int jd[kTileG];
+                bool miss = false;
+#pragma unroll
+                for (int it = 0; it < kTileG; ++it) {
+                    const int r = it * kRowsPerPass + (lane / kTileG);
+                    const int cg = lane % kTileG;
+                    const int cb = 4 * cg;
+                    const int rsw = r ^ (cg * kTileSwz);
+                    int4 v = make_int4(tile[(cb + 0) * kLaneStride + rsw], tile[(cb + 1) * kLaneStride + rsw],
+                                       tile[(cb + 2) * kLaneStride + rsw], tile[(cb + 3) * kLaneStride + rsw]);
+                    if (__builtin_expect(any_wasted, 0)) v = shl4(v, __builtin_amdgcn_ds_bpermute(r << 2, wasted));
+                    int4 q = x[it];
+                    if constexpr (F32) {
+                        const float2 fg = row_fg[r];
+                        q = make_int4(quantise_f32(__int_as_float(q.x), fg.x, fg.y), quantise_f32(__int_as_float(q.y), fg.x, fg.y),
+                                      quantise_f32(__int_as_float(q.z), fg.x, fg.y), quantise_f32(__int_as_float(q.w), fg.x, fg.y));
+                    }
+                    jd[it] = (v.x != q.x) ? 0 : (v.y != q.y) ? 1 : (v.z != q.z) ? 2 : (v.w != q.w) ? 3 : 4;
+                    miss = miss || (jd[it] < 4);
+                }
+                if (__builtin_expect(__any(miss), 0)) {
+#pragma unroll
+                    for (int it = 0; it < kTileG; ++it)
+                        report(it * kRowsPerPass + (lane / kTileG), rout[it] + tbase + 4 * (lane % kTileG), jd[it]);
+                }
+                __builtin_amdgcn_wave_barrier();
+                return;
+            }
+        } else if (all_al && tbase >= lo_max && tbase + kTileW <= hi_min) {
             // the whole tile lies inside every row's range and every row is 16-byte aligned: plain vector stores (for the
             // float32 output too: the restore of utils.c:364 with the row's offset and 1 / gain)
 #pragma unroll
@@ -1334,10 +1420,21 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             if (__builtin_expect(any_wasted, 0)) v = shl4(v, __builtin_amdgcn_ds_bpermute(r << 2, wasted));
             const int2 rg = make_int2(__builtin_amdgcn_ds_bpermute(r << 2, lo), __builtin_amdgcn_ds_bpermute(r << 2, hi));
             const int si = tbase + cb;
+            int jd = 4;  // (compare sink)
             if (si + 3 >= rg.x && si < rg.y) {
                 const int64_t ob = rout[it] + si;
                 const bool fullv = (si >= rg.x) && (si + 3 < rg.y) && out_aligned && ((ob & 3) == 0);
-                if constexpr (F32) {
+                if constexpr (SINK) {
+                    if (fullv) {
+                        const int4 x = input4(ob, r);
+                        jd = (v.x != x.x) ? 0 : (v.y != x.y) ? 1 : (v.z != x.z) ? 2 : (v.w != x.w) ? 3 : 4;
+                    } else {  // (highest column first: the smallest differing one is what remains)
+                        if (si + 3 >= rg.x && si + 3 < rg.y && input1(ob + 3, r) != v.w) jd = 3;
+                        if (si + 2 >= rg.x && si + 2 < rg.y && input1(ob + 2, r) != v.z) jd = 2;
+                        if (si + 1 >= rg.x && si + 1 < rg.y && input1(ob + 1, r) != v.y) jd = 1;
+                        if (si + 0 >= rg.x && si + 0 < rg.y && input1(ob + 0, r) != v.x) jd = 0;
+                    }
+                } else if constexpr (F32) {
                     const float2 fg = row_fg[r];
                     float4 o;
                     o.x = __fadd_rn(fg.x, __fmul_rn(fg.y, (float)v.x));  // utils.c:364
@@ -1361,6 +1458,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                     }
                 }
             }
+            if constexpr (SINK) report(r, rout[it] + si, jd);
         }
         __builtin_amdgcn_wave_barrier();
     };
@@ -1526,6 +1624,24 @@ __global__ __launch_bounds__(256) void verbatim_channel0_kernel(DecodeArgs a) {
 // reference's int64 value is (channel 1 << 32) | (channel 0 as unsigned) (utils.c:96-123), and the
 // optional float64 restore is offsets + (1 / gains) * value (int64_to_float64, utils.c:329-348).
 // ------------------------------------------------------------------------------------------
+// sample i of a task's planar image (low words t0 / t1, bit 32 in h0 / h1), channels combined: the reference's int64 value
+__device__ __forceinline__ int64_t combine_sample(const int32_t* t0, const int32_t* t1, const uint32_t* h0, const uint32_t* h1, int asg,
+                                                  int64_t i) {
+    // 33-bit two's complement: low word plus bit 32, which is also the sign
+    const int64_t c0 = (int64_t)(uint64_t)(uint32_t)t0[i] | (((h0[i >> 5] >> (i & 31)) & 1u) ? (int64_t)0xFFFFFFFF00000000LL : 0);
+    const int64_t c1 = (int64_t)(uint64_t)(uint32_t)t1[i] | (((h1[i >> 5] >> (i & 31)) & 1u) ? (int64_t)0xFFFFFFFF00000000LL : 0);
+    int64_t L, R;
+    if (asg == 1) { L = c0; R = c1; }
+    else if (asg == 8) { L = c0; R = c0 - c1; }
+    else if (asg == 9) { R = c1; L = c0 + c1; }
+    else {
+        const int64_t mid = (int64_t)((uint64_t)c0 << 1) | (c1 & 1);
+        L = (mid + c1) >> 1;
+        R = (mid - c1) >> 1;
+    }
+    return (int64_t)(((uint64_t)R << 32) | (uint64_t)(uint32_t)L);
+}
+
 __global__ __launch_bounds__(256) void combine_channels_kernel(DecodeArgs a, int64_t* __restrict__ out_i64,
                                                                double* __restrict__ out_f64, const double* __restrict__ offsets64,
                                                                const double* __restrict__ gains64) {
@@ -1558,22 +1674,43 @@ __global__ __launch_bounds__(256) void combine_channels_kernel(DecodeArgs a, int
     double off = 0.0, coeff = 1.0;
     if (out_f64) { off = offsets64[s]; coeff = 1.0 / gains64[s]; }
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-        // 33-bit two's complement: low word plus bit 32, which is also the sign
-        const int64_t c0 = (int64_t)(uint64_t)(uint32_t)t0[i] | (((h0[i >> 5] >> (i & 31)) & 1u) ? (int64_t)0xFFFFFFFF00000000LL : 0);
-        const int64_t c1 = (int64_t)(uint64_t)(uint32_t)t1[i] | (((h1[i >> 5] >> (i & 31)) & 1u) ? (int64_t)0xFFFFFFFF00000000LL : 0);
-        int64_t L, R;
-        if (asg == 1) { L = c0; R = c1; }
-        else if (asg == 8) { L = c0; R = c0 - c1; }
-        else if (asg == 9) { R = c1; L = c0 + c1; }
-        else {
-            const int64_t mid = (int64_t)((uint64_t)c0 << 1) | (c1 & 1);
-            L = (mid + c1) >> 1;
-            R = (mid - c1) >> 1;
-        }
-        const int64_t v = (int64_t)(((uint64_t)R << 32) | (uint64_t)(uint32_t)L);
+        const int64_t v = combine_sample(t0, t1, h0, h1, asg, i);
         const int64_t o = out_off + (fstart - sl_first) + i;
         if (out_f64) out_f64[o] = off + coeff * (double)v;
         else out_i64[o] = v;
+    }
+}
+
+// K8C: the compare sink of two-channel arrays (grid mode over whole streams).  The channels are combined as K8 combines
+// them and compared with a.cmp: int64, or float64 quantised with offsets64 / gains64 by the encoder's own arithmetic
+// (quantise_f64).  A thread lowers a.first_mismatch[stream] to the first differing sample it meets; a frame K7 rejected
+// (no channel assignment) lowers it to the frame's first sample.
+__global__ __launch_bounds__(256) void compare_channels_kernel(DecodeArgs a, const double* __restrict__ offsets64,
+                                                               const double* __restrict__ gains64) {
+    const int64_t task = blockIdx.x;
+    const int64_t s = task / a.nfr, f = task - s * a.nfr;
+    const int64_t fstart = f * (int64_t)a.B;
+    const int asg = a.assign[task];
+    if (asg < 0) {
+        if (threadIdx.x == 0) atomicMin(a.first_mismatch + s, (unsigned long long)fstart);
+        return;
+    }
+    int64_t bs = a.stream_size - fstart;
+    if (bs > a.B) bs = a.B;
+    const int32_t* t0 = a.out_i32 + (task * 2 + 0) * (int64_t)a.B;
+    const int32_t* t1 = a.out_i32 + (task * 2 + 1) * (int64_t)a.B;
+    const uint32_t* h0 = a.hibits + (task * 2 + 0) * (int64_t)a.hib_words;
+    const uint32_t* h1 = a.hibits + (task * 2 + 1) * (int64_t)a.hib_words;
+    const int64_t* in_i64 = static_cast<const int64_t*>(a.cmp) + s * a.stream_size + fstart;
+    const double* in_f64 = static_cast<const double*>(a.cmp) + s * a.stream_size + fstart;
+    double off = 0.0, gain = 1.0;
+    if (offsets64) { off = offsets64[s]; gain = gains64[s]; }
+    for (int64_t i = threadIdx.x; i < bs; i += 256) {
+        const int64_t x = offsets64 ? quantise_f64(in_f64[i], off, gain) : in_i64[i];
+        if (combine_sample(t0, t1, h0, h1, asg, i) != x) {
+            atomicMin(a.first_mismatch + s, (unsigned long long)(fstart + i));
+            break;  // (this thread's later samples lie behind it)
+        }
     }
 }
 

@@ -95,6 +95,7 @@ std::mutex g_mu;
 std::map<int, std::unique_ptr<DeviceState>> g_dev;
 std::atomic<bool> g_prof{false};
 std::atomic<bool> g_verify{false};  // fa_set_decode_verify: re-compute every decoded frame's CRC-16
+std::atomic<bool> g_encode_verify{false};  // fa_set_encode_verify: the host encoders compare each chunk's streams with its input
 
 DeviceState* dev_state() {
     int d = 0;
@@ -515,7 +516,15 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
                        const float* d_gains, hipStream_t st, int nch = 1, int64_t* d_out_i64 = nullptr, double* d_out_f64 = nullptr,
                        const double* d_offsets64 = nullptr, const double* d_gains64 = nullptr, DecodeIndex* idx = nullptr,
                        bool build_only = false, int verify = -1, void* h_copy = nullptr, size_t h_copy_bytes = 0,
-                       bool* h_copied = nullptr) {
+                       bool* h_copied = nullptr, const void* d_cmp = nullptr, int64_t* d_first_mismatch = nullptr) {
+    // compare sink (d_first_mismatch != null): whole streams through K7 in grid mode, the caller's samples at d_cmp in place
+    // of an output (float32 / float64 when offsets / gains are given); a frame that is rejected or cannot be located marks
+    // its stream instead of setting the error word, so only errors of the stream headers are returned
+    const bool cmp = (d_first_mismatch != nullptr);
+#ifdef FA_DEV_MINIMAL
+    if (cmp) return FA_ERROR_CONVERT_TYPE;
+#endif
+    if (cmp) verify = 0;
     int rc = FA_ERROR_NONE;
     int h_err[4] = {0, 0, 0, 0};
     bool err_cleared = true;  // (the one-off path clears them before K6)
@@ -621,6 +630,8 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     a.blob = d_bytes; a.blob_bytes = n_bytes; a.meta = d_meta; a.ftab = d_ftab; a.nf = nf; a.B = B;
     a.stream_size = stream_size;
     a.out_i32 = d_out_i32; a.out_f32 = d_out_f32; a.offsets = d_offsets; a.gains = d_gains; a.err = d_err;
+    a.cmp = d_cmp; a.first_mismatch = reinterpret_cast<unsigned long long*>(d_first_mismatch);
+    if (cmp) FA_HIP_TRY(hipMemsetAsync(d_first_mismatch, 0xFF, (size_t)n_stream * 8, st));  // -1: no difference (yet)
     if (n_slices < 0) {
         a.f0 = first_decode / B;
         const int64_t f1 = (first_decode + n_decode - 1) / B;
@@ -692,9 +703,9 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     }
     if (a.B > kMaxBlock * 16) return FA_ERROR_DECODE_INIT;
     const unsigned nblk = (unsigned)((a.n_tasks + 63) / 64);
-    const bool f32 = (d_out_f32 != nullptr);
+    const bool f32 = cmp ? (d_offsets != nullptr) : (d_out_f32 != nullptr);
     const bool f64 = (d_out_f64 != nullptr);
-    if (a.B <= kLatMaxBlock && latency_allowed(a.n_tasks)) {
+    if (!cmp && a.B <= kLatMaxBlock && latency_allowed(a.n_tasks)) {
         LatWide wd;
         wd.out_i64 = d_out_i64; wd.out_f64 = d_out_f64; wd.offsets = d_offsets64; wd.gains = d_gains64;
         auto launch_latency = [&](const DecodeArgs& aa, int* flag) {
@@ -801,21 +812,31 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
             hipLaunchKernelGGL(verbatim_channel0_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a);
             a.verbatim_done = 1;
         }
-        hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        // (compare: the same decode, but a frame it rejects marks its stream -- K8C cannot tell a frame abandoned half way)
+        if (cmp) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 2, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         prof_end(2, st);
         FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(hipStreamSynchronize(st));
-        if (h_err[1] & kFlagNeed16) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        if (h_err[1] & kFlagNeed16) {
+            if (cmp) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 2, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+            else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        }
         if (h_err[1]) {  // a frame left over by the 16-deep pass raises the flag again
             FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
             FA_HIP_TRY(hipStreamSynchronize(st));
         }
-        if (h_err[1] & kFlagNeed32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        hipLaunchKernelGGL(combine_channels_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a, d_out_i64, d_out_f64, d_offsets64,
-                           d_gains64);
+        if (h_err[1] & kFlagNeed32) {
+            if (cmp) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 2, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+            else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        }
+        if (cmp) hipLaunchKernelGGL(compare_channels_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a, d_offsets64, d_gains64);
+        else hipLaunchKernelGGL(combine_channels_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a, d_out_i64, d_out_f64, d_offsets64,
+                                d_gains64);
         FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(hipStreamSynchronize(st));
         FA_HIP_TRY(hipGetLastError());
+        if (cmp) return h_err[0] & ~(kErrDecodeProcess | kErrDecodeSeek);
         if ((rc = run_verify(a, d_err, h_err, st, verify))) return rc;
         return h_err[0];
     }
@@ -835,7 +856,10 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     const bool verifying_k7 = (verify < 0 ? g_verify.load() : verify != 0);
     const bool beside = verifying_k7 && a.n_tasks >= 16384 && std::getenv("FLACARRAY_HIP_VERIFY_AFTER") == nullptr &&
                         run_verify_beside_begin(st);
-    if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    if (cmp) {
+        if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     prof_end(2, st);
     if (beside) {
@@ -846,11 +870,17 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
     if (h_err[1] & kFlagNeed16) {
-        if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        if (cmp) {
+            if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+            else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     }
     if (h_err[1] & kFlagNeed32) {
-        if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        if (cmp) {
+            if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+            else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     }
     if (h_err[1]) {
@@ -858,6 +888,7 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         FA_HIP_TRY(hipStreamSynchronize(st));
     }
     FA_HIP_TRY(hipGetLastError());
+    if (cmp) return h_err[0] & ~(kErrDecodeProcess | kErrDecodeSeek);
     if ((rc = run_verify(a, d_err, h_err, st, verify))) return rc;
     return h_err[0];
 #endif
@@ -963,6 +994,11 @@ int fa_abi_version(void) { return FA_ABI_VERSION; }
 
 int fa_set_decode_verify(int on) {
     const bool was = g_verify.exchange(on != 0);
+    return was ? 1 : 0;
+}
+
+int fa_set_encode_verify(int on) {
+    const bool was = on < 0 ? g_encode_verify.load() : g_encode_verify.exchange(on != 0);
     return was ? 1 : 0;
 }
 
@@ -1702,6 +1738,36 @@ int fa_decode_slices_i64_device(const unsigned char* d_bytes, int64_t n_bytes, c
                               reinterpret_cast<hipStream_t>(stream), 2, d_out_i64, d_out_f64, d_offsets, d_gains, nullptr, false, verify);
 }
 
+static int compare_device(int nch, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                          int64_t n_stream, int64_t stream_size, const void* d_data, const void* d_offsets, const void* d_gains,
+                          int64_t* d_first_mismatch, void* stream) {
+    FA_API_LOCK;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
+    if (!d_data || !d_first_mismatch || (d_offsets == nullptr) != (d_gains == nullptr)) return FA_ERROR_CONVERT_TYPE;
+    const float* off32 = nch == 1 ? static_cast<const float*>(d_offsets) : nullptr;
+    const float* gain32 = nch == 1 ? static_cast<const float*>(d_gains) : nullptr;
+    const double* off64 = nch == 2 ? static_cast<const double*>(d_offsets) : nullptr;
+    const double* gain64 = nch == 2 ? static_cast<const double*>(d_gains) : nullptr;
+    return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, 0, stream_size, -1, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, off32, gain32, reinterpret_cast<hipStream_t>(stream), nch, nullptr, nullptr, off64,
+                              gain64, nullptr, false, 0, nullptr, 0, nullptr, d_data, d_first_mismatch);
+}
+
+int fa_compare_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                          int64_t n_stream, int64_t stream_size, const void* d_data, const float* d_offsets, const float* d_gains,
+                          int64_t* d_first_mismatch, void* stream) {
+    return compare_device(1, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, d_data, d_offsets, d_gains, d_first_mismatch,
+                          stream);
+}
+
+int fa_compare_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                          int64_t n_stream, int64_t stream_size, const void* d_data, const double* d_offsets, const double* d_gains,
+                          int64_t* d_first_mismatch, void* stream) {
+    return compare_device(2, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, d_data, d_offsets, d_gains, d_first_mismatch,
+                          stream);
+}
+
 int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t stream_size, const float* d_quanta,
                                int32_t* d_output, float* d_offsets, float* d_gains, void* stream) {
     FA_API_LOCK;
@@ -1943,7 +2009,9 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     FA_HIP_TRY(hipGetDevice(&dev));
     const unsigned char* data = reinterpret_cast<const unsigned char*>(data_v);
     const size_t stream_bytes = (size_t)stream_size * 4 * (size_t)nch;
-    const int64_t chunk = host_chunk_streams(n_stream, stream_bytes, 0x7fffffffLL / one.nf);
+    const bool verifying = g_encode_verify.load();
+    // (verifying two-channel chunks also takes the decoder's planar image, as large again as the chunk's input)
+    const int64_t chunk = host_chunk_streams(n_stream, stream_bytes * (verifying && nch == 2 ? 2 : 1), 0x7fffffffLL / one.nf);
     const int64_t n_chunks = (n_stream + chunk - 1) / chunk;
     const bool fused_f32 = f32 && fused_geometry(chunk, stream_size, level, true) &&
                            (n_stream % chunk == 0 || fused_geometry(n_stream % chunk, stream_size, level, true));
@@ -1956,7 +2024,7 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     const int64_t wsb = single_pass_workspace_for(chunk, stream_size, level, nch);  // (the slot sequence's size when that is forced)
     if (wsb < 0) return FA_ERROR_ENCODE_PROCESS;
     if ((rc = get_scratch(5, (size_t)wsb, &d_ws))) return rc;
-    if ((rc = get_scratch(4, (size_t)chunk * 40 + 1024, &d_aux))) return rc;
+    if ((rc = get_scratch(4, (size_t)chunk * 48 + 1024, &d_aux))) return rc;
     int64_t* d_starts = reinterpret_cast<int64_t*>(d_aux);
     int64_t* d_nb = d_starts + chunk;
     float* d_q = reinterpret_cast<float*>(d_nb + chunk);
@@ -1965,6 +2033,8 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     double* d_q64 = reinterpret_cast<double*>(d_nb + chunk);  // (the float64 form uses the same region: three doubles per stream)
     double* d_off64 = d_q64 + chunk;
     double* d_gain64 = d_off64 + chunk;
+    int64_t* d_mm = reinterpret_cast<int64_t*>(d_gain64 + chunk);  // encode verification: first mismatch per stream
+    std::vector<int64_t> h_mm(verifying ? (size_t)chunk : 0);
     const int64_t cap_chunk = capacity_bytes_for(chunk, stream_size, level, nch);
     if ((rc = get_scratch(3, (size_t)cap_chunk + 256, &d_out))) return rc;
     if (((f32 && !fused_f32) || f64) && (rc = get_scratch(11, in_b + 256, &d_int))) return rc;
@@ -2038,6 +2108,21 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
             }
             err = fa_encode_i64_device(reinterpret_cast<const int64_t*>(src64), ns, stream_size, level, d_ws, wsb, reinterpret_cast<unsigned char*>(d_out),
                                        cap_chunk, d_starts, d_nb, &total, nullptr, nullptr);
+            if (err) break;
+        }
+        if (verifying) {
+            // decode what was just written and compare it with the input slot (float input through the offsets / gains the
+            // encoder used): nothing crosses the link again but one word per stream
+            const void *voff = nullptr, *vgain = nullptr;
+            if (f32) { voff = d_off; vgain = d_gain; }
+            if (f64) { voff = d_off64; vgain = d_gain64; }
+            err = compare_device(nch, reinterpret_cast<const unsigned char*>(d_out), total, d_starts, d_nb, ns, stream_size, d_in, voff, vgain,
+                                 d_mm, nullptr);
+            if (!err && hipMemcpy(h_mm.data(), d_mm, (size_t)ns * 8, hipMemcpyDeviceToHost) != hipSuccess) err = FA_ERROR_DEVICE;
+            for (int64_t i = 0; i < ns && !err; ++i)
+                if (h_mm[i] >= 0) err = FA_ERROR_ENCODE_VERIFY;
+            if (err & (FA_ERROR_DECODE_INIT | FA_ERROR_DECODE_PROCESS | FA_ERROR_DECODE_SEEK))
+                err = FA_ERROR_ENCODE_VERIFY;  // (a stream the decoder cannot read back is a failed verification)
             if (err) break;
         }
         if (n_chunks > 1) {

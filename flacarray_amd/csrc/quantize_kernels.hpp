@@ -224,6 +224,12 @@ FA_GLOBAL __global__ __launch_bounds__(256) void int32_to_float32_kernel(const i
 }
 
 // ---- float64 <-> int64 (utils.c:245-348): every operation is a double operation ------------------
+// one sample, utils.c:316-323
+__device__ __forceinline__ int64_t quantise_f64(double x, double off, double gain) {
+    const double t = x - off;
+    return (t >= 0.0) ? x86_cvtt_i64(gain * t + 0.5) : x86_cvtt_i64(gain * t - 0.5);
+}
+
 FA_GLOBAL __global__ __launch_bounds__(1024) void float64_to_int64_kernel(const double* __restrict__ input, int64_t stream_size,
                                                                 const double* __restrict__ quanta, int64_t* __restrict__ output,
                                                                 double* __restrict__ offsets, double* __restrict__ gains,
@@ -283,10 +289,7 @@ FA_GLOBAL __global__ __launch_bounds__(1024) void float64_to_int64_kernel(const 
     }
     __syncthreads();
     const double off = s_off, gain = s_gain;
-    for (int64_t i = tid; i < stream_size; i += 1024) {
-        const double t = in[i] - off;
-        out[i] = (t >= 0.0) ? x86_cvtt_i64(gain * t + 0.5) : x86_cvtt_i64(gain * t - 0.5);  // :316-323
-    }
+    for (int64_t i = tid; i < stream_size; i += 1024) out[i] = quantise_f64(in[i], off, gain);
 }
 
 FA_GLOBAL __global__ __launch_bounds__(256) void int64_to_float64_kernel(const int64_t* __restrict__ input, int64_t stream_size,

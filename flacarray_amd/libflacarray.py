@@ -183,6 +183,54 @@ def wrap_int64_to_float64(idata, n_stream, stream_size, offsets, gains):
     return wrap_int32_to_float32(idata, n_stream, stream_size, offsets, gains, _f64=True)
 
 
+_encode_verify_lock = threading.Lock()
+
+
+def set_encode_verify(on):
+    """Process-wide DEFAULT of verification after encode, used by the host encode calls whose `verify` argument is None
+    (encode_flac, array_compress, FlacArray.from_array) and by FlacArray.from_device_array: when on, every chunk of
+    streams is decoded on the device right after it is written and compared with its input -- libFLAC's encoder verify
+    mode (FLAC__stream_encoder_set_verify) -- and a difference raises RuntimeError.  What is compared is the integers:
+    float input as quantised with the stored offsets and gains.  Returns the previous setting; initially off.  Callers of
+    the reference's C entry points (encode_i32, encode_i64, ...) get verification through this default alone."""
+    with _encode_verify_lock:
+        return bool(_lib.lib().fa_set_encode_verify(1 if on else 0))
+
+
+def _encode_verify_default():
+    return bool(_lib.lib().fa_set_encode_verify(-1))
+
+
+class _EncodeVerify:
+    """Hold the library's encode-verify setting at `verify` for one host encode call (None: the default as it is).  One
+    Python lock covers set, call and restore; the library serialises host encodes anyway."""
+
+    def __init__(self, verify):
+        self.verify = verify
+
+    def __enter__(self):
+        if self.verify is not None:
+            _encode_verify_lock.acquire()
+            self.prev = _lib.lib().fa_set_encode_verify(1 if self.verify else 0)
+        return self
+
+    def __exit__(self, *exc):
+        if self.verify is not None:
+            _lib.lib().fa_set_encode_verify(self.prev)
+            _encode_verify_lock.release()
+        return False
+
+
+def _check_encode(errcode):
+    if errcode & _lib.ERROR_NAN_INPUT:
+        raise RuntimeError("Cannot convert data with NaNs to integers")
+    if errcode & _lib.ERROR_ENCODE_VERIFY:
+        raise RuntimeError("Encoding verification failed: the compressed streams do not decode to the input "
+                           f"(return code = {errcode})")
+    if errcode != 0:
+        raise RuntimeError(f"Encoding failed, return code = {errcode}")
+
+
 def _wrap_encode(fn, flatdata, n_stream, stream_size, level, dtype=np.int32):
     _lib.require_device()
     flatdata = np.ascontiguousarray(flatdata, dtype=dtype)
@@ -191,8 +239,7 @@ def _wrap_encode(fn, flatdata, n_stream, stream_size, level, dtype=np.int32):
     n_bytes = ctypes.c_int64(0)
     raw = ctypes.c_void_p(None)
     errcode = fn(_ptr(flatdata), n_stream, stream_size, level, ctypes.byref(n_bytes), _ptr(flat_starts), ctypes.byref(raw))
-    if errcode != 0:
-        raise RuntimeError(f"Encoding failed, return code = {errcode}")
+    _check_encode(errcode)
     flat_nbytes[:-1] = np.diff(flat_starts)
     flat_nbytes[-1] = n_bytes.value - flat_starts[-1]
     return (_adopt_malloc(raw.value, n_bytes.value), flat_starts, flat_nbytes)
@@ -225,10 +272,7 @@ def encode_flac_f32(data, quanta, level):
     raw = ctypes.c_void_p(None)
     errcode = _lib.lib().fa_encode_f32_host(_ptr(data), n_stream, stream_size, level, _ptr(q) if q is not None else None,
                                             ctypes.byref(n_bytes), _ptr(flat_starts), ctypes.byref(raw), _ptr(offsets), _ptr(gains))
-    if errcode & _lib.ERROR_NAN_INPUT:
-        raise RuntimeError("Cannot convert data with NaNs to integers")
-    if errcode != 0:
-        raise RuntimeError(f"Encoding failed, return code = {errcode}")
+    _check_encode(errcode)
     flat_nbytes[:-1] = np.diff(flat_starts)
     flat_nbytes[-1] = n_bytes.value - flat_starts[-1]
     return (_adopt_malloc(raw.value, n_bytes.value), flat_starts.reshape(lead), flat_nbytes.reshape(lead), offsets.reshape(lead),
@@ -262,10 +306,7 @@ def encode_flac_f64(data, quanta, level):
     raw = ctypes.c_void_p(None)
     errcode = _lib.lib().fa_encode_f64_host(_ptr(data), n_stream, stream_size, level, _ptr(q) if q is not None else None,
                                             ctypes.byref(n_bytes), _ptr(flat_starts), ctypes.byref(raw), _ptr(offsets), _ptr(gains))
-    if errcode & _lib.ERROR_NAN_INPUT:
-        raise RuntimeError("Cannot convert data with NaNs to integers")
-    if errcode != 0:
-        raise RuntimeError(f"Encoding failed, return code = {errcode}")
+    _check_encode(errcode)
     flat_nbytes[:-1] = np.diff(flat_starts)
     flat_nbytes[-1] = n_bytes.value - flat_starts[-1]
     return (_adopt_malloc(raw.value, n_bytes.value), flat_starts.reshape(lead), flat_nbytes.reshape(lead), offsets.reshape(lead),
@@ -349,11 +390,13 @@ def wrap_encode_i64_threaded(flatdata, n_stream, stream_size, level):
 
 
 
-def encode_flac(data, level, use_threads=False):
+def encode_flac(data, level, use_threads=False, verify=None):
     """Compress an integer array to FLAC streams (libflacarray.pyx:529-594).
 
     Returns (compressed bytestream, stream starting bytes, stream nbytes); starts and nbytes
-    have the leading shape of `data` and are at least 1-D.
+    have the leading shape of `data` and are at least 1-D.  `verify`: True = decode what was written, on the device,
+    and compare it with the input before returning (libFLAC's verify mode; a difference raises RuntimeError), False =
+    do not, None = the default of set_encode_verify.
     """
     if data.dtype != flac_i32_dtype and data.dtype != flac_i64_dtype:
         raise RuntimeError("Only 32bit or 64bit integer data is supported")
@@ -374,7 +417,8 @@ def encode_flac(data, level, use_threads=False):
         enc = wrap_encode_i64_threaded if use_threads else wrap_encode_i64
     else:
         enc = wrap_encode_i32_threaded if use_threads else wrap_encode_i32
-    compressed, flatstarts, flatnbytes = enc(flatdata, n_stream, stream_size, level)
+    with _EncodeVerify(verify):
+        compressed, flatstarts, flatnbytes = enc(flatdata, n_stream, stream_size, level)
     return (compressed, flatstarts.reshape(starts_shape), flatnbytes.reshape(starts_shape))
 
 
@@ -520,7 +564,7 @@ class EncodeWorkspace:
         return self.buf
 
 
-def encode_flac_device(data, level=5, workspace=None, return_info=False, compact=False, capacity_bytes=None):
+def encode_flac_device(data, level=5, workspace=None, return_info=False, compact=False, capacity_bytes=None, verify=False):
     """Encode a C-contiguous int32 (or int64: two-channel streams) CUDA tensor [..., stream_size] held in HBM.
 
     Returns (compressed uint8 tensor, starts int64 tensor, nbytes int64 tensor), all on the
@@ -534,7 +578,18 @@ def encode_flac_device(data, level=5, workspace=None, return_info=False, compact
     (1.016 x the input: every frame VERBATIM): if the blob does not fit, nothing outside the buffer is written and the
     call raises "Encoding failed, return code = 1" (ERROR_ALLOC) -- retry without it.  Under FLACARRAY_HIP_SLOTS (the
     diagnostic cross-check) everything runs the slot sequence (K3, K4, K5) and returns an exact-size tensor.
+
+    `verify=True`: the streams are decoded and compared with `data` on the device before the call returns
+    (compare_flac_device); a difference raises RuntimeError naming the first differing stream(s) and sample.  The
+    returned bytes are the same either way.
     """
+    out = _encode_flac_device(data, level, workspace, return_info, compact, capacity_bytes)
+    if verify:
+        _raise_on_mismatch(compare_flac_device(out[0], out[1], out[2], data))
+    return out
+
+
+def _encode_flac_device(data, level, workspace, return_info, compact, capacity_bytes):
     torch = _torch()
     if data.dtype != torch.int32 and data.dtype != torch.int64:
         raise RuntimeError("Only 32bit or 64bit integer data is supported")
@@ -653,7 +708,7 @@ def _precision_quanta_device(data, precision):
     return torch.from_numpy(q).to(data.device)
 
 
-def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=False, precision=None):
+def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=False, precision=None, verify=False):
     """Quantise and encode a C-contiguous float32 CUDA tensor [..., stream_size] held in HBM: the device-resident
     analogue of array_compress on float32 input (compress.py:50-84 -> float_to_int + encode_flac).
 
@@ -662,7 +717,16 @@ def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=F
     the single-pass kernel applies (levels 3-8, stream length a multiple of 4096) the quantisation happens in the
     encoder's staging load after a range pre-pass -- the int32 array never exists in HBM; otherwise the two steps
     run one after the other.  Same bytes, offsets and gains either way.  `precision` p (instead of `quanta`): quanta =
-    std / 10^p per stream as array_compress derives them (std_device, then the host path's numpy expression)."""
+    std / 10^p per stream as array_compress derives them (std_device, then the host path's numpy expression).
+    `verify=True`: compare the streams with `data` before returning, as encode_flac_device does -- the quantised integers,
+    not the floats."""
+    out = _encode_flac_device_f32(data, quanta, level, workspace, compact, precision)
+    if verify:
+        _raise_on_mismatch(compare_flac_device(out[0], out[1], out[2], data, out[3], out[4]))
+    return out
+
+
+def _encode_flac_device_f32(data, quanta, level, workspace, compact, precision):
     torch = _torch()
     if data.dtype != torch.float32 or not data.is_contiguous():
         raise ValueError("Only float32 and float64 data are supported")
@@ -713,13 +777,14 @@ def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=F
     return compressed, starts.reshape(lead), nbytes.reshape(lead), offsets.reshape(lead), gains.reshape(lead)
 
 
-def encode_flac_device_f64(data, quanta=None, level=5, workspace=None, compact=False, precision=None):
+def encode_flac_device_f64(data, quanta=None, level=5, workspace=None, compact=False, precision=None, verify=False):
     """Quantise and encode a C-contiguous float64 CUDA tensor [..., stream_size] held in HBM: the device-resident
     analogue of array_compress on float64 input (float64_to_int64, then the two-channel encoder).
 
     `quanta`: None (per-stream quanta from the data range) or a tensor with one value per stream; `precision` p
     instead: quanta = std / 10^p per stream, as for encode_flac_device_f32.  Returns (compressed, starts, nbytes,
-    offsets, gains), offsets / gains float64 with the leading shape of `data`."""
+    offsets, gains), offsets / gains float64 with the leading shape of `data`.  `verify=True`: compare the streams with
+    `data` before returning (the quantised integers, not the floats)."""
     torch = _torch()
     if data.dtype != torch.float64 or not data.is_contiguous():
         raise ValueError("Only float32 and float64 data are supported")
@@ -733,7 +798,80 @@ def encode_flac_device_f64(data, quanta=None, level=5, workspace=None, compact=F
         quanta = _precision_quanta_device(data, precision)
     ints, offsets, gains = float64_to_int64_device(data, quanta)
     comp, st, nb = encode_flac_device(ints, level=level, workspace=workspace, compact=compact)
+    if verify:
+        _raise_on_mismatch(compare_flac_device(comp, st, nb, data, offsets, gains))
     return comp, st, nb, offsets, gains
+
+
+def _raise_on_mismatch(first):
+    """RuntimeError naming the first streams whose entry in `first` (compare_flac_device's result) is not -1."""
+    m = first.reshape(-1).cpu().numpy()
+    bad = np.flatnonzero(m >= 0)
+    if bad.size:
+        where = ", ".join(f"stream {i} at sample {m[i]}" for i in bad[:4])
+        more = f" and {bad.size - 4} more stream(s)" if bad.size > 4 else ""
+        raise RuntimeError(f"Encoding verification failed: the compressed streams do not decode to the input ({where}{more})")
+
+
+def compare_flac_device(compressed, starts, nbytes, data, offsets=None, gains=None):
+    """Compare device-resident FLAC streams with the samples they should decode to, without a decoded copy: the decoder
+    compares each sample with `data` where it would store it.  Returns an int64 tensor with the shape of `starts`, one
+    entry per stream: the index of the first sample that differs, or -1.
+
+    `data`: a C-contiguous tensor of shape (n_stream, stream_size) or starts.shape + (stream_size,) on the device of
+    `compressed` -- int32 or float32 against one-channel streams, int64 or float64 against two-channel streams.  Float
+    data need the store's `offsets` and `gains` and are quantised with them exactly as the encoder quantises: what is
+    compared is the quantised integers, not the floats, so a float change that leaves its quantised integer the same is
+    not a mismatch.  Streams of any origin compare (without a SEEKTABLE the frames are found by a sync scan).  A frame
+    the decoder rejects marks its stream at that frame's first sample or earlier; the other streams are still compared.
+    Damaged stream headers raise RuntimeError, as decode_flac_device does.  All streams must share one block size (every
+    store this library writes does); a store whose streams differ raises RuntimeError ("Comparison failed, return code =
+    8192"), where decode_flac_device would decode it in one launch per block size."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64:
+        raise ValueError("starts and nbytes should be of type int64")
+    if starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes must have the same shape")
+    n_stream = int(np.prod(starts.shape))
+    if data.dtype not in (torch.int32, torch.int64, torch.float32, torch.float64):
+        raise ValueError(f"Unsupported data type '{data.dtype}': int32, int64, float32 or float64")
+    if data.dim() == 0 or data.shape[-1] <= 0:
+        raise ValueError("data needs a non-empty stream axis")
+    stream_size = int(data.shape[-1])
+    if tuple(data.shape) not in ((n_stream, stream_size), tuple(starts.shape) + (stream_size,)) and not (data.dim() == 1 and n_stream == 1):
+        raise ValueError(f"data of shape {tuple(data.shape)} does not match {n_stream} streams (starts of shape {tuple(starts.shape)})")
+    if not data.is_contiguous():
+        raise ValueError("Only C-contiguous data is supported")
+    is_float = data.dtype in (torch.float32, torch.float64)
+    if (offsets is None) != (gains is None):
+        raise ValueError("When specifying offsets, you must also provide the gains")
+    if is_float and offsets is None:
+        raise ValueError("Comparing float data needs the store's offsets and gains")
+    if not is_float and offsets is not None:
+        raise ValueError("offsets and gains apply to float data only")
+    if is_float and (offsets.numel() != n_stream or gains.numel() != n_stream):
+        raise ValueError("offsets and gains need one value per stream")
+    dev = compressed.device
+    if not (compressed.is_cuda and data.device == dev and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("compare_flac_device needs compressed, starts, nbytes and data on the same GPU")
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    wide = data.dtype in (torch.int64, torch.float64)
+    if is_float:
+        offsets = offsets.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+        gains = gains.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+    first = torch.empty(starts.shape, dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    with _on_device(dev):
+        errcode = (L.fa_compare_i64_device if wide else L.fa_compare_i32_device)(
+            _dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, _dp(data), _dp(offsets),
+            _dp(gains), _dp(first), _stream_ptr(),
+        )
+    if errcode != 0:
+        raise RuntimeError(f"Comparison failed, return code = {errcode}")
+    return first
 
 
 def _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, is_int64):

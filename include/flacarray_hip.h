@@ -38,6 +38,7 @@ extern "C" {
 /* additions of this library */
 #define FA_ERROR_DEVICE (1 << 24)   /* a HIP runtime call failed (no GPU, out of memory, ...) */
 #define FA_ERROR_NAN_INPUT (1 << 25) /* float32_to_int32 saw a NaN */
+#define FA_ERROR_ENCODE_VERIFY (1 << 26) /* encode verification: a stream does not decode to its input (fa_set_encode_verify) */
 
 /* ---------------------------------------------------------------------------------------
  * Group 1: host-pointer drop-ins for the reference C ABI
@@ -234,6 +235,31 @@ void fa_pinned_free(void* p);
  * FLACARRAY_HIP_HOST_VERIFY=0 turns that off).  The header CRC-8 of every frame is checked in all cases. */
 int fa_set_decode_verify(int on);
 
+/* Verification after encode, the counterpart of libFLAC's FLAC__stream_encoder_set_verify: when on, the host-pointer
+ * encoders (encode_i32[_threaded], encode_i64[_threaded], fa_encode_f32_host, fa_encode_f64_host) decode every chunk of
+ * streams they have just written, still on the device, and compare it with the chunk's input (float input as the
+ * integers its offsets / gains quantise it to) before the input slot is released; a difference, or a stream the decoder
+ * cannot read back, fails the call with FA_ERROR_ENCODE_VERIFY.  Process-wide; returns the previous setting (on < 0:
+ * returns the setting and leaves it); initially off. */
+int fa_set_encode_verify(int on);
+
+/* Compare device-resident streams with the samples they should decode to, without writing the decoded samples anywhere:
+ * d_first_mismatch[n_stream] (device) receives, per stream, the index of the first sample that differs, or -1.  What is
+ * compared is integers: d_data is int32 for fa_compare_i32_device and int64 for fa_compare_i64_device, or -- when
+ * d_offsets / d_gains [n_stream] are given -- float32 / float64 quantised with them exactly as the encoder does, so a
+ * float change that leaves its quantised integer unchanged is not a difference.  Any stream the decoder reads is accepted
+ * (streams without a SEEKTABLE are located by the sync scan).  A frame the decoder rejects, or cannot locate, marks its
+ * stream at that frame's first sample or earlier and the other streams are still compared; only errors of the stream
+ * headers (fLaC marker, STREAMINFO, stream size) are returned as the decoder's error bits, and so is a store whose streams
+ * differ in block size (FA_ERROR_DECODE_INIT, as the decode entry points return it).  Device memory: the frame
+ * table, and for two-channel streams the planar image fa_decode_i64_device uses too.  Synchronises the stream. */
+int fa_compare_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                          int64_t n_stream, int64_t stream_size, const void* d_data, const float* d_offsets, const float* d_gains,
+                          int64_t* d_first_mismatch, void* stream);
+int fa_compare_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                          int64_t n_stream, int64_t stream_size, const void* d_data, const double* d_offsets, const double* d_gains,
+                          int64_t* d_first_mismatch, void* stream);
+
 /* Batched random access: slice i is samples [first[i], first[i]+count[i]) of stream
  * slice_stream[i]; its samples are written at element offset out_offset[i] of the output.
  * The four slice arrays are HOST arrays of length n_slices.  The reference needs one
@@ -297,10 +323,11 @@ const char* fa_version(void);
 
 /* ABI revision of the group-2 (fa_*) signatures in this header.  It is raised whenever an existing entry point changes
  * its argument list (revision 2: the trailing `int verify` of the device decode entry points, 1 / 0 / negative = check /
- * do not / process default, see fa_set_decode_verify; revision 3 added the std entry points); a binding built against
+ * do not / process default, see fa_set_decode_verify; revision 3 added the std entry points, revision 4 the compare entry
+ * points and fa_set_encode_verify); a binding built against
  * another revision must refuse the library instead of calling it with a shifted argument list --
  * flacarray_amd/_lib.py does. */
-#define FA_ABI_VERSION 3  /* (revision 3: fa_stream_std_f32_device / fa_stream_std_f64_device) */
+#define FA_ABI_VERSION 4  /* (revision 4: fa_compare_i32_device / fa_compare_i64_device / fa_set_encode_verify) */
 int fa_abi_version(void);
 
 #ifdef __cplusplus
