@@ -11,6 +11,7 @@ from .compress import array_compress
 from .decompress import array_decompress, array_decompress_slice
 from .libflacarray import (
     DeviceDecodeIndex,
+    append_flac_device,
     compare_flac_device,
     decode_flac,
     decode_flac_device,
@@ -35,6 +36,7 @@ __version__ = "0.1.0"
 __all__ = [
     "FlacArray",
     "DeviceDecodeIndex",
+    "append_flac_device",
     "array_compress",
     "array_decompress",
     "array_decompress_slice",

@@ -38,6 +38,14 @@ SYMBOLS = [
     "fa_encode_capacity_bytes_i64",
     "fa_encode_single_pass_workspace_bytes_i64",
     "fa_encode_i64_device",
+    "fa_append_workspace_bytes",
+    "fa_append_workspace_bytes_i64",
+    "fa_append_capacity_bytes",
+    "fa_append_capacity_bytes_i64",
+    "fa_append_i32_device",
+    "fa_append_i64_device",
+    "fa_quantise_f32_device",
+    "fa_quantise_f64_device",
     "fa_float64_to_int64_device",
     "fa_int64_to_float64_device",
     "fa_decode_slices_i64_device",
@@ -142,6 +150,18 @@ def lib():
     L.fa_decode_i32_device.restype = cint
     L.fa_decode_slices_i32_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, cint]
     L.fa_decode_slices_i32_device.restype = cint
+    for name in ("fa_append_workspace_bytes", "fa_append_workspace_bytes_i64"):
+        getattr(L, name).argtypes = [i64, i64, i64, u32]
+        getattr(L, name).restype = i64
+    for name in ("fa_append_capacity_bytes", "fa_append_capacity_bytes_i64"):
+        getattr(L, name).argtypes = [i64, i64, i64, i64, u32]
+        getattr(L, name).restype = i64
+    for name in ("fa_append_i32_device", "fa_append_i64_device"):
+        getattr(L, name).argtypes = [vp, i64, vp, vp, i64, i64, vp, i64, u32, vp, i64, vp, i64, vp, vp, pi64, vp]
+        getattr(L, name).restype = cint
+    for name in ("fa_quantise_f32_device", "fa_quantise_f64_device"):
+        getattr(L, name).argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
+        getattr(L, name).restype = cint
     L.fa_float32_to_int32_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp]
     L.fa_float32_to_int32_device.restype = cint
     L.fa_int32_to_float32_device.argtypes = [vp, i64, i64, vp, vp, vp, vp]

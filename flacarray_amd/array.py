@@ -401,6 +401,89 @@ class FlacArray:
         first = compare_flac_device(comp, st, nb, x.reshape(self._st.count, self._stream_size), off, gain)
         return first.cpu().numpy().reshape(self._leading_shape)
 
+    def append(self, data, level=5, verify=None):
+        """Extend every stream by data.shape[-1] samples, in place; returns self (addition to the reference API).
+
+        `data`: a numpy array or a torch tensor on the device, of shape leading_shape + (n,) ((n,) for a 1-D array) and
+        of this array's dtype; n == 0 does nothing.  Integer arrays: after any sequence of appends the store (every byte
+        of `compressed`, `stream_starts`, `stream_nbytes`) is the one from_array(concatenation, level=level) writes, for
+        any split into chunks -- provided `level` is the level the store was written at (the store does not record it;
+        a level of another block size raises ValueError).  Float arrays: the new samples are quantised with the store's
+        own `stream_offsets` and `stream_gains`, which do not change (a NaN raises RuntimeError, out-of-range values
+        become INT_MIN as in float_to_int): the store is the integer encode of the old integers followed by these, NOT
+        from_array of the concatenated floats, whose offsets and gains would differ.  Hence no `quanta` / `precision`.
+
+        The old short last frame of every stream is decoded, encoded again with the new samples, and spliced in behind
+        the kept old frames on the device (append_flac_device); each append copies the whole compressed blob once.  A
+        resident array (to_device / from_device_array) stays resident, with an exact-size copy of the new blob, and its
+        decode index is rebuilt on next use; any other array uploads its store, appends on the device and brings the
+        result back.  Either way the new blob is also copied to the host mirror that answers `compressed`: at GB sizes
+        that PCIe transfer (and, for a host array, the upload) costs more than the device work.  The store is replaced, not
+        changed: a FlacArray(self) copy made before still holds the old one.  `verify`: decode the re-encoded span and
+        compare it with its input on the device before returning (None = the default of set_encode_verify).  Streams
+        without this library's SEEKTABLE (libFLAC-written) raise ValueError; a store assembled by `dist` (global shape
+        other than the local one) raises NotImplementedError."""
+        import torch
+
+        from .libflacarray import _encode_verify_default, append_flac_device
+
+        st = self._st
+        if st.global_shape != st.grid:
+            raise NotImplementedError("append is not supported for a store that is one part of a distributed array")
+        is_tensor = isinstance(data, torch.Tensor)
+        dt = np.dtype(str(data.dtype).replace("torch.", "")) if is_tensor else np.asarray(data).dtype
+        if dt != st.dtype:
+            raise ValueError(f"data of dtype {dt} does not match the array's dtype {st.dtype}")
+        shape = tuple(int(k) for k in data.shape)
+        if len(shape) != len(st.shape) or shape[:-1] != tuple(st.shape[:-1]):
+            raise ValueError(f"data of shape {shape} does not match the array's leading shape {tuple(st.shape[:-1])}")
+        if level < 0 or level > 8:
+            raise ValueError("FLAC only supports compression levels 0-8")
+        n = shape[-1]
+        if n == 0:
+            return self
+        # the layout the splice needs, checked on the host copy: STREAMINFO, then the SEEKTABLE (last) of one point per frame
+        B = 1152 if level <= 2 else 4096
+        blob = np.asarray(st.blob, dtype=np.uint8)
+        s0 = np.asarray(st.starts, dtype=np.int64).reshape(-1)
+        nb = np.asarray(st.nbytes_per_stream, dtype=np.int64).reshape(-1)
+        if np.any(nb < 46) or np.any(s0 < 0) or np.any(s0 + nb > blob.size):
+            raise ValueError("the store's stream index does not fit its compressed bytes")
+        at = lambda k: blob[s0 + k].astype(np.int64)  # noqa: E731
+        bs = (at(8) << 8) | at(9)
+        stl = (at(43) << 16) | (at(44) << 8) | at(45)
+        if np.any(at(4) != 0) or np.any(at(42) != 0x83) or np.any(stl != 18 * (-(-st.samples // np.maximum(bs, 1)))):
+            raise ValueError("append needs streams written by this library (a SEEKTABLE with one point per frame); "
+                             "libFLAC-written streams are not supported")
+        if np.any(bs != B):
+            raise ValueError(f"level {level} has block size {B}, the store's streams have {int(bs[bs != B][0])}: append at the store's level")
+        if verify is None:
+            verify = _encode_verify_default()
+        res = self._resident
+        if res is not None:
+            dev = res["device"]
+            comp, starts, nbytes, off, gain = res["compressed"], res["starts"], res["nbytes"], res["offsets"], res["gains"]
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            up = lambda a, t: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=t).reshape(-1)).to(dev)  # noqa: E731
+            ft = np.float64 if st.wide else np.float32
+            comp, starts, nbytes = up(blob, np.uint8), up(s0, np.int64), up(nb, np.int64)
+            off, gain = up(st.offsets, ft), up(st.gains, ft)
+        x = data.to(dev) if is_tensor else torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+        x = x.reshape(st.count, n).contiguous()
+        # (a resident store keeps an exact-size blob, as from_device_array does; a host store only copies the bytes back)
+        comp2, starts2, nbytes2 = append_flac_device(comp, starts, nbytes, st.samples, x, level=level, offsets=off, gains=gain, verify=verify,
+                                                     compact=res is not None)
+        ishape = np.shape(st.starts)
+        new = _Store.build(tuple(st.shape[:-1]) + (st.samples + n,), None, st.dtype, comp2.cpu().numpy(),
+                           starts2.cpu().numpy().reshape(ishape), nbytes2.cpu().numpy().reshape(ishape), st.offsets, st.gains, st.dist)
+        if res is not None:
+            if res.get("index") is not None:
+                res["index"].close()
+            self._resident = dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), index=None)
+        self._st = new
+        return self
+
     @classmethod
     def from_device_array(cls, data, level=5, quanta=None, precision=None, verify=None):
         """Construct a RESIDENT FlacArray from a torch tensor that already lives in HBM (int32 / int64, or float32 /

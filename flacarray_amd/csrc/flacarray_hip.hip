@@ -37,6 +37,7 @@
 #include "quantize_kernels.hpp"
 #include "verify_kernels.hpp"
 #include "std_kernels.hpp"
+#include "append_kernels.hpp"
 
 namespace {
 
@@ -1551,6 +1552,193 @@ int fa_encode_i64_device(const int64_t* d_data, int64_t n_stream, int64_t stream
     }
     return placed_encode_run(d32, 2, n_stream, stream_size, level, d_workspace, workspace_bytes, d_bytes, capacity_bytes, d_starts, d_nbytes,
                              h_total_bytes, d_info, stream);
+}
+
+// ---- append (append_kernels.hpp): tail decode, encode of tail + new samples, splice -----------------------------------
+// Workspace layout (256-byte aligned regions): the (n_stream, r + n) integer image the encode reads, the decoded tails,
+// the encode's blob (its capacity), its starts | nbytes, the kept old bytes per stream, the error word and total, and
+// the encode's own workspace.
+struct AppendPlan {
+    int64_t B, r, base, nf_old, m, nf_enc, enc_cap, enc_ws;
+    size_t off_cat, off_tail, off_blob, off_idx, off_kept, off_small, off_ws, total;
+};
+static int make_append_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level, AppendPlan* pl) {
+    if (level > 8) return FA_ERROR_INVALID_LEVEL;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0 || n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    pl->B = (level <= 2) ? 1152 : 4096;
+    pl->r = stream_size % pl->B;
+    pl->base = stream_size / pl->B;
+    pl->nf_old = (stream_size + pl->B - 1) / pl->B;
+    pl->m = pl->r + n;
+    pl->nf_enc = (pl->m + pl->B - 1) / pl->B;
+    pl->enc_cap = capacity_bytes_for(n_stream, pl->m, level, nch);
+    pl->enc_ws = single_pass_workspace_for(n_stream, pl->m, level, nch);
+    if (pl->enc_cap < 0 || pl->enc_ws < 0) return FA_ERROR_ENCODE_INIT;
+    const size_t elt = 4 * (size_t)nch;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t o = 0;
+    pl->off_cat = o; o += (pl->r > 0) ? up((size_t)n_stream * (size_t)pl->m * elt) : 0;
+    pl->off_tail = o; o += up((size_t)n_stream * (size_t)pl->r * elt);
+    pl->off_blob = o; o += up((size_t)pl->enc_cap + 64);
+    pl->off_idx = o; o += up((size_t)n_stream * 16);
+    pl->off_kept = o; o += up((size_t)n_stream * 8);
+    pl->off_small = o; o += 256;
+    pl->off_ws = o; o += up((size_t)pl->enc_ws);
+    pl->total = o;
+    return FA_ERROR_NONE;
+}
+
+static int64_t append_workspace_for(int nch, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
+    AppendPlan pl;
+    return make_append_plan(nch, n_stream, stream_size, n, level, &pl) ? -1 : (int64_t)pl.total;
+}
+// every stream grows by at most the bytes of its new encode plus 6 bytes per renumbered frame (the stream header of the
+// result is never longer than the two it replaces)
+static int64_t append_capacity_for(int nch, int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
+    AppendPlan pl;
+    if (make_append_plan(nch, n_stream, stream_size, n, level, &pl)) return -1;
+    return n_old_bytes + pl.enc_cap + 6 * pl.nf_enc * n_stream + 64;
+}
+
+static int append_run(int nch, const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                      int64_t n_stream, int64_t stream_size, const void* d_data, int64_t n, uint32_t level, void* d_workspace,
+                      int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
+                      int64_t* h_total_bytes, void* stream) {
+    FA_API_LOCK;
+    AppendPlan pl;
+    int rc = make_append_plan(nch, n_stream, stream_size, n, level, &pl);
+    if (rc) return rc;
+    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
+    if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
+    // (the splice reads its sources in aligned 16-byte blocks)
+    if ((reinterpret_cast<uintptr_t>(d_old) & 15) || (reinterpret_cast<uintptr_t>(d_workspace) & 15) || !d_data) return FA_ERROR_ENCODE_INIT;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* ws = reinterpret_cast<char*>(d_workspace);
+    const size_t elt = 4 * (size_t)nch;
+    char* cat = ws + pl.off_cat;
+    // 0. every old stream must be one this encoder wrote with the call's block size, channel count and stream size
+    AppendArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.old = d_old; a.old_bytes = n_old_bytes; a.old_starts = d_old_starts; a.old_nbytes = d_old_nbytes;
+    a.kept = reinterpret_cast<int64_t*>(ws + pl.off_kept);
+    a.starts = d_starts; a.nbytes = d_nbytes; a.out = d_bytes; a.capacity = capacity_bytes;
+    a.err = reinterpret_cast<int*>(ws + pl.off_small);
+    a.n_stream = n_stream; a.old_size = stream_size; a.new_size = stream_size + n; a.base = pl.base; a.nf_old = pl.nf_old; a.nf_enc = pl.nf_enc;
+    a.B = (int32_t)pl.B; a.nch = nch;
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
+    hipLaunchKernelGGL(append_check_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
+    {
+        int h_err = 0;
+        FA_HIP_TRY(hipMemcpyAsync(&h_err, a.err, sizeof h_err, hipMemcpyDeviceToHost, st));
+        FA_HIP_TRY(hipStreamSynchronize(st));
+        FA_HIP_TRY(hipGetLastError());
+        if (h_err) return FA_ERROR_DECODE_INIT;
+    }
+    // 1. the old short last frame of every stream, decoded (the existing decoders), in front of the new samples
+    if (pl.r > 0) {
+        void* tail = ws + pl.off_tail;
+        rc = (nch == 2) ? fa_decode_i64_device(d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, pl.base * pl.B, stream_size,
+                                               reinterpret_cast<int64_t*>(tail), nullptr, nullptr, nullptr, stream, -1)
+                        : fa_decode_i32_device(d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, pl.base * pl.B, stream_size,
+                                               reinterpret_cast<int32_t*>(tail), nullptr, nullptr, nullptr, stream, -1);
+        if (rc) return rc;
+        FA_HIP_TRY(hipMemcpy2DAsync(cat, (size_t)pl.m * elt, tail, (size_t)pl.r * elt, (size_t)pl.r * elt, (size_t)n_stream, hipMemcpyDeviceToDevice, st));
+        FA_HIP_TRY(hipMemcpy2DAsync(cat + (size_t)pl.r * elt, (size_t)pl.m * elt, d_data, (size_t)n * elt, (size_t)n * elt, (size_t)n_stream,
+                                    hipMemcpyDeviceToDevice, st));
+    } else {
+        cat = reinterpret_cast<char*>(const_cast<void*>(d_data));  // (no old tail: the new samples are the encode's input as they are)
+    }
+    // 2. encode tail + new samples (K3F / K3G / the slot sequence, as for any array)
+    unsigned char* blob = reinterpret_cast<unsigned char*>(ws + pl.off_blob);
+    int64_t* e_idx = reinterpret_cast<int64_t*>(ws + pl.off_idx);
+    int64_t enc_total = 0;
+    rc = (nch == 2) ? fa_encode_i64_device(reinterpret_cast<const int64_t*>(cat), n_stream, pl.m, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap,
+                                           e_idx, e_idx + n_stream, &enc_total, nullptr, stream)
+                    : fa_encode_i32_device(reinterpret_cast<const int32_t*>(cat), n_stream, pl.m, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap,
+                                           e_idx, e_idx + n_stream, &enc_total, nullptr, stream);
+    if (rc) return rc;
+    // 3. sizes, starts (one wait: the error word and the total), then the splice
+    a.enc = blob; a.enc_bytes = enc_total; a.enc_starts = e_idx; a.enc_nbytes = e_idx + n_stream;
+    int64_t* d_total = reinterpret_cast<int64_t*>(ws + pl.off_small + 8);
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
+    hipLaunchKernelGGL(append_size_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_nbytes, n_stream, d_starts, d_total);
+    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
+    FA_HIP_TRY(hipMemcpyAsync(&back, a.err, sizeof back, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (back.err) return FA_ERROR_DECODE_INIT;  // (checked above already; the new encode's index is checked here)
+    if (back.total > capacity_bytes) return FA_ERROR_ALLOC;
+    // workgroups per stream: ~64 KB of the result each (at most 1024, and a grid of fewer than 2^23 workgroups)
+    int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, back.total / n_stream / 65536));
+    while (parts > 1 && n_stream * parts >= (1LL << 23)) parts >>= 1;
+    if (n_stream * parts >= (1LL << 31) / 256) return FA_ERROR_ALLOC;
+    a.parts = (int32_t)parts;
+    hipLaunchKernelGGL(append_splice_kernel, dim3((unsigned)(n_stream * parts)), dim3(256), 0, st, a);
+    FA_HIP_TRY(hipGetLastError());
+    *h_total_bytes = back.total;
+    return FA_ERROR_NONE;
+}
+
+}  // extern "C" (a template needs C++ linkage)
+template <typename F, typename I>
+static int quantise_given_run(const F* d_in, int64_t n_stream, int64_t n, const F* d_offsets, const F* d_gains, I* d_out, int64_t out_stride,
+                              void* stream) {
+    FA_API_LOCK;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    if (!d_in || !d_offsets || !d_gains || !d_out || out_stride < n) return FA_ERROR_CONVERT_TYPE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    void* p = nullptr;
+    int rc = get_scratch(4, 256, &p);
+    if (rc) return rc;
+    int* d_flags = reinterpret_cast<int*>(p);
+    FA_HIP_TRY(hipMemsetAsync(d_flags, 0, 4, st));
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(16384, (n_stream * n + 1023) / 1024));
+    hipLaunchKernelGGL((quantise_rows_kernel<F, I>), dim3((unsigned)blocks), dim3(256), 0, st, d_in, n_stream, n, d_offsets, d_gains, d_out,
+                       out_stride, d_flags);
+    int h = 0;
+    FA_HIP_TRY(hipMemcpyAsync(&h, d_flags, 4, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    return (h & 1) ? FA_ERROR_NAN_INPUT : FA_ERROR_NONE;
+}
+extern "C" {
+
+int64_t fa_append_workspace_bytes(int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
+    return append_workspace_for(1, n_stream, stream_size, n, level);
+}
+int64_t fa_append_workspace_bytes_i64(int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
+    return append_workspace_for(2, n_stream, stream_size, n, level);
+}
+int64_t fa_append_capacity_bytes(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
+    return append_capacity_for(1, n_old_bytes, n_stream, stream_size, n, level);
+}
+int64_t fa_append_capacity_bytes_i64(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
+    return append_capacity_for(2, n_old_bytes, n_stream, stream_size, n, level);
+}
+int fa_append_i32_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                         int64_t n_stream, int64_t stream_size, const int32_t* d_data, int64_t n, uint32_t level, void* d_workspace,
+                         int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
+                         int64_t* h_total_bytes, void* stream) {
+    return append_run(1, d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, d_data, n, level, d_workspace, workspace_bytes,
+                      d_bytes, capacity_bytes, d_starts, d_nbytes, h_total_bytes, stream);
+}
+int fa_append_i64_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                         int64_t n_stream, int64_t stream_size, const int64_t* d_data, int64_t n, uint32_t level, void* d_workspace,
+                         int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
+                         int64_t* h_total_bytes, void* stream) {
+    return append_run(2, d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, d_data, n, level, d_workspace, workspace_bytes,
+                      d_bytes, capacity_bytes, d_starts, d_nbytes, h_total_bytes, stream);
+}
+int fa_quantise_f32_device(const float* d_input, int64_t n_stream, int64_t n, const float* d_offsets, const float* d_gains, int32_t* d_output,
+                           int64_t out_stride, void* stream) {
+    return quantise_given_run<float, int32_t>(d_input, n_stream, n, d_offsets, d_gains, d_output, out_stride, stream);
+}
+int fa_quantise_f64_device(const double* d_input, int64_t n_stream, int64_t n, const double* d_offsets, const double* d_gains, int64_t* d_output,
+                           int64_t out_stride, void* stream) {
+    return quantise_given_run<double, int64_t>(d_input, n_stream, n, d_offsets, d_gains, d_output, out_stride, stream);
 }
 
 int fa_decode_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts,

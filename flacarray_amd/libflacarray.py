@@ -1175,3 +1175,97 @@ def float64_to_int64_device(data, quanta=None):
     if errcode != 0:
         raise RuntimeError(f"Encoding failed, return code = {errcode}")
     return out, offsets.reshape(lead), gains.reshape(lead)
+
+
+def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, offsets=None, gains=None, verify=False, compact=False):
+    """Extend every stream of a device-resident store by data.shape[-1] samples: returns the new (compressed, starts,
+    nbytes), all on the device, the store's arguments left as they are.
+
+    The store must have this library's layout (one SEEKTABLE point per frame) and `level` the level it was written at
+    (its block size is checked against the streams' STREAMINFO).  `data`: a C-contiguous tensor on the store's device,
+    (n_stream, n) or starts.shape + (n,) -- int32 for one-channel streams, int64 for two-channel streams; or float32 /
+    float64 with the store's `offsets` and `gains`, which then quantise it exactly as the encoder quantises (a NaN raises
+    RuntimeError).  The result is byte for byte the encode of the concatenated integers (fa_append_i32_device /
+    fa_append_i64_device, include/flacarray_hip.h): the old short last frame is decoded, the new frames are encoded
+    and spliced in behind the kept old ones.  `compressed` is a view of a buffer sized for the worst case (the old blob
+    plus a verbatim encode of the new frames), which it keeps alive; `compact=True` returns an exact-size copy instead, as
+    encode_flac_device does.  A store whose STREAMINFO names another block size, channel count (one for int32 / float32
+    data, two for int64 / float64) or stream size than the call's raises ValueError before anything is decoded.
+    `verify=True`: decode the re-encoded span, samples [stream_size - r, stream_size + n) (r = the old short tail), and
+    compare it with the old tail and the new integers; a difference raises RuntimeError."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64 or starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes should be int64 tensors of one shape")
+    if level < 0 or level > 8:
+        raise ValueError("FLAC only supports compression levels 0-8")
+    n_stream = int(np.prod(starts.shape))
+    if data.dim() == 0:
+        raise ValueError("data needs a stream axis")
+    n = int(data.shape[-1])
+    if tuple(data.shape) not in ((n_stream, n), tuple(starts.shape) + (n,)) and not (data.dim() == 1 and n_stream == 1):
+        raise ValueError(f"data of shape {tuple(data.shape)} does not match {n_stream} streams (starts of shape {tuple(starts.shape)})")
+    is_float = data.dtype in (torch.float32, torch.float64)
+    if data.dtype not in (torch.int32, torch.int64) and not is_float:
+        raise ValueError(f"Unsupported data type '{data.dtype}': int32, int64, float32 or float64")
+    if is_float != (offsets is not None) or (offsets is None) != (gains is None):
+        raise ValueError("float data need the store's offsets and gains, integer data take neither")
+    dev = compressed.device
+    if not (compressed.is_cuda and data.device == dev and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("append_flac_device needs compressed, starts, nbytes and data on the same GPU")
+    if n == 0:
+        return compressed, starts, nbytes
+    wide = data.dtype in (torch.int64, torch.float64)
+    L = _lib.lib()
+    data = data.reshape(n_stream, n).contiguous()
+    with _on_device(dev):
+        if is_float:
+            off = offsets.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+            gain = gains.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+            if off.numel() != n_stream or gain.numel() != n_stream:
+                raise ValueError("offsets and gains need one value per stream")
+            ints = torch.empty((n_stream, n), dtype=torch.int64 if wide else torch.int32, device=dev)
+            errcode = (L.fa_quantise_f64_device if wide else L.fa_quantise_f32_device)(
+                _dp(data), n_stream, n, _dp(off), _dp(gain), _dp(ints), n, _stream_ptr())
+            if errcode & _lib.ERROR_NAN_INPUT:
+                raise RuntimeError("Cannot convert data with NaNs to integers")
+            if errcode != 0:
+                raise RuntimeError(f"Quantisation failed, return code = {errcode}")
+            data = ints
+        comp = compressed.contiguous()
+        st, nb = starts.reshape(-1).contiguous(), nbytes.reshape(-1).contiguous()
+        ws_bytes = (L.fa_append_workspace_bytes_i64 if wide else L.fa_append_workspace_bytes)(n_stream, stream_size, n, level)
+        cap = (L.fa_append_capacity_bytes_i64 if wide else L.fa_append_capacity_bytes)(comp.numel(), n_stream, stream_size, n, level)
+        if ws_bytes < 0 or cap < 0:
+            raise RuntimeError("Appending failed: invalid geometry")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        buf = torch.empty(cap, dtype=torch.uint8, device=dev)
+        index = torch.empty(2 * n_stream, dtype=torch.int64, device=dev)
+        total = ctypes.c_int64(0)
+        errcode = (L.fa_append_i64_device if wide else L.fa_append_i32_device)(
+            _dp(comp), comp.numel(), _dp(st), _dp(nb), n_stream, stream_size, _dp(data), n, level, _dp(ws), ws_bytes, _dp(buf), cap,
+            _dp(index[:n_stream]), _dp(index[n_stream:]), ctypes.byref(total), _stream_ptr())
+    if errcode == 8192:  # FA_ERROR_DECODE_INIT
+        raise ValueError("Appending needs streams written by this library (a SEEKTABLE with one point per frame) with the block size of "
+                         f"level {level}, {2 if wide else 1} channel(s) ({data.dtype} data) and {stream_size} samples")
+    if errcode != 0:
+        raise RuntimeError(f"Appending failed, return code = {errcode}")
+    blob = buf[: total.value]
+    if compact:
+        blob = blob.clone()
+        del buf
+    out = (blob, index[:n_stream].reshape(starts.shape), index[n_stream:].reshape(starts.shape))
+    if verify:
+        B = 1152 if level <= 2 else 4096
+        lo = stream_size - stream_size % B
+        span = decode_flac_device(out[0], out[1], out[2], stream_size + n, lo, stream_size + n, is_int64=wide, verify=True).reshape(n_stream, -1)
+        want = data
+        if lo < stream_size:
+            old = decode_flac_device(comp, st, nb, stream_size, lo, stream_size, is_int64=wide).reshape(n_stream, -1)
+            want = torch.cat([old, data], dim=1)
+        bad = (span != want).any(dim=1)
+        if bool(bad.any()):
+            first = torch.where(bad, (span != want).int().argmax(dim=1) + lo, torch.full_like(bad, -1, dtype=torch.int64))
+            _raise_on_mismatch(first)
+    return out

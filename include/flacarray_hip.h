@@ -182,6 +182,43 @@ int fa_encode_i64_device(const int64_t* d_data, int64_t n_stream, int64_t stream
                          int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
                          int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info, void* stream);
 
+/* Append: extend every stream of a device-resident store (written by this library: one SEEKTABLE point per frame) by
+ * n samples -- d_data[n_stream][n], int32 for one-channel streams (fa_append_i32_device), int64 for two-channel streams
+ * (fa_append_i64_device) -- so that the result is, byte for byte, what fa_encode_i32_device / fa_encode_i64_device writes for
+ * the concatenation (same level: its block size must be the one in the streams' STREAMINFO).  The old short last frame of
+ * every stream is decoded, the (n_stream, r + n) image of it and the new samples is encoded, and one splice kernel writes the
+ * result: a new stream header, the kept old frames verbatim, the new frames renumbered (UTF-8 frame number, CRC-8 and --
+ * through the linear CRC identity, without a pass over the payload -- CRC-16).  d_old is 16-byte aligned and unchanged; the
+ * caller owns it, d_data, the workspace (fa_append_workspace_bytes[_i64]: the integer image, the encode's blob and its own
+ * workspace) and d_bytes (fa_append_capacity_bytes[_i64] bytes: the old blob, the new encode's worst case and 6 bytes per new
+ * frame; a smaller buffer gives FA_ERROR_ALLOC if the result does not fit, nothing outside it written).  The result is
+ * d_bytes[0, *h_total_bytes), d_starts, d_nbytes [n_stream].  The call waits on `stream` for the tail decode and for the
+ * total; the splice may still be queued when it returns: d_bytes / d_starts / d_nbytes are complete, and the workspace is
+ * free again, when `stream` reaches the end of the call's work.  FA_ERROR_DECODE_INIT (before anything is decoded or
+ * encoded): a stream without this encoder's SEEKTABLE, or whose STREAMINFO names another block size, channel count (1 for
+ * the _i32 call, 2 for the _i64 call) or total sample count than stream_size. */
+int64_t fa_append_workspace_bytes(int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level);
+int64_t fa_append_workspace_bytes_i64(int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level);
+int64_t fa_append_capacity_bytes(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level);
+int64_t fa_append_capacity_bytes_i64(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level);
+int fa_append_i32_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                         int64_t n_stream, int64_t stream_size, const int32_t* d_data, int64_t n, uint32_t level, void* d_workspace,
+                         int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
+                         int64_t* h_total_bytes, void* stream);
+int fa_append_i64_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                         int64_t n_stream, int64_t stream_size, const int64_t* d_data, int64_t n, uint32_t level, void* d_workspace,
+                         int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
+                         int64_t* h_total_bytes, void* stream);
+
+/* Quantisation with GIVEN per-stream offsets and gains (the inner loop of float32_to_int32 / float64_to_int64, utils.c:229-240
+ * and :316-323, without the range pass): d_output[s * out_stride + i] for d_input[n_stream][n]; out_stride >= n lets the caller
+ * write into a wider image.  What an append to a float store quantises its new samples with.  FA_ERROR_NAN_INPUT for a NaN
+ * (the outputs are then unspecified).  Synchronises the stream. */
+int fa_quantise_f32_device(const float* d_input, int64_t n_stream, int64_t n, const float* d_offsets, const float* d_gains, int32_t* d_output,
+                           int64_t out_stride, void* stream);
+int fa_quantise_f64_device(const double* d_input, int64_t n_stream, int64_t n, const double* d_offsets, const double* d_gains, int64_t* d_output,
+                           int64_t out_stride, void* stream);
+
 /* Decode [first_sample,last_sample) (or everything when either is negative) of n_stream
  * streams.  Exactly one of d_out_i32 / d_out_f32 is non-NULL; with d_out_f32 the int32 ->
  * float32 restore (utils.c:350-368) is fused into the store and d_offsets/d_gains[n_stream]
