@@ -12,6 +12,7 @@ from .decompress import array_decompress, array_decompress_slice
 from .libflacarray import (
     DeviceDecodeIndex,
     append_flac_device,
+    check_md5_device,
     compare_flac_device,
     decode_flac,
     decode_flac_device,
@@ -22,11 +23,14 @@ from .libflacarray import (
     encode_flac_device_f64,
     float32_to_int32_device,
     float64_to_int64_device,
+    md5_device,
     set_decode_verify,
+    set_encode_md5,
     set_encode_verify,
+    sign_streams_device,
     std_device,
 )
-from .utils import float_to_int, int_to_float, keep_select
+from .utils import float_to_int, int_to_float, keep_select, stream_md5
 
 array_encode = array_compress
 array_decode = array_decompress
@@ -50,6 +54,11 @@ __all__ = [
     "decode_flac_device",
     "decode_slices_device",
     "compare_flac_device",
+    "md5_device",
+    "check_md5_device",
+    "sign_streams_device",
+    "stream_md5",
+    "set_encode_md5",
     "float32_to_int32_device",
     "float64_to_int64_device",
     "std_device",

@@ -60,6 +60,11 @@ SYMBOLS = [
     "fa_set_encode_verify",
     "fa_compare_i32_device",
     "fa_compare_i64_device",
+    "fa_md5_i32_device",
+    "fa_md5_i64_device",
+    "fa_sign_streams_device",
+    "fa_check_md5_device",
+    "fa_set_encode_md5",
     "fa_encode_f32_host",
     "fa_encode_f64_host",
     "fa_decode_f32_host",
@@ -197,6 +202,15 @@ def lib():
     for name in ("fa_compare_i32_device", "fa_compare_i64_device"):
         getattr(L, name).argtypes = [vp, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp]
         getattr(L, name).restype = cint
+    for name in ("fa_md5_i32_device", "fa_md5_i64_device"):
+        getattr(L, name).argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, cint, vp, vp]
+        getattr(L, name).restype = cint
+    L.fa_sign_streams_device.argtypes = [vp, i64, vp, i64, vp, vp]
+    L.fa_sign_streams_device.restype = cint
+    L.fa_check_md5_device.argtypes = [vp, i64, vp, vp, i64, i64, cint, i64, vp, vp, vp, cint]
+    L.fa_check_md5_device.restype = cint
+    L.fa_set_encode_md5.argtypes = [cint]
+    L.fa_set_encode_md5.restype = cint
     L.fa_profile_enable.argtypes = [cint]
     L.fa_profile_enable.restype = None
     L.fa_profile_last.argtypes = [ctypes.POINTER(ctypes.c_float)]

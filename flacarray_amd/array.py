@@ -16,7 +16,7 @@ import numpy as np
 
 from .compress import array_compress
 from .decompress import array_decompress_slice
-from .utils import log
+from .utils import log, stream_md5
 
 _KINDS = {"int32": (False, False), "int64": (True, False), "float32": (False, True), "float64": (True, True)}
 
@@ -401,7 +401,7 @@ class FlacArray:
         first = compare_flac_device(comp, st, nb, x.reshape(self._st.count, self._stream_size), off, gain)
         return first.cpu().numpy().reshape(self._leading_shape)
 
-    def append(self, data, level=5, verify=None):
+    def append(self, data, level=5, verify=None, md5=False):
         """Extend every stream by data.shape[-1] samples, in place; returns self (addition to the reference API).
 
         `data`: a numpy array or a torch tensor on the device, of shape leading_shape + (n,) ((n,) for a 1-D array) and
@@ -422,7 +422,11 @@ class FlacArray:
         changed: a FlacArray(self) copy made before still holds the old one.  `verify`: decode the re-encoded span and
         compare it with its input on the device before returning (None = the default of set_encode_verify).  Streams
         without this library's SEEKTABLE (libFLAC-written) raise ValueError; a store assembled by `dist` (global shape
-        other than the local one) raises NotImplementedError."""
+        other than the local one) raises NotImplementedError.
+
+        The splice writes a fresh stream header, so the appended store comes out UNSIGNED (`md5` all zero) even if the
+        old one was signed: a finished digest cannot be resumed.  `md5=True` is append followed by sign(): correct, at the
+        cost of one decode of the whole store; explicit only (it does not follow set_encode_md5)."""
         import torch
 
         from .libflacarray import _encode_verify_default, append_flac_device
@@ -441,7 +445,7 @@ class FlacArray:
             raise ValueError("FLAC only supports compression levels 0-8")
         n = shape[-1]
         if n == 0:
-            return self
+            return self.sign() if md5 else self
         # the layout the splice needs, checked on the host copy: STREAMINFO, then the SEEKTABLE (last) of one point per frame
         B = 1152 if level <= 2 else 4096
         blob = np.asarray(st.blob, dtype=np.uint8)
@@ -482,17 +486,70 @@ class FlacArray:
                 res["index"].close()
             self._resident = dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), index=None)
         self._st = new
+        return self.sign() if md5 else self
+
+    def _device_store(self):
+        """(device, compressed, starts, nbytes) for a pass over the whole store: the resident tensors, or an upload."""
+        import torch
+
+        res = self._resident
+        if res is not None:
+            return res["device"], res["compressed"], res["starts"], res["nbytes"]
+        dev = torch.device("cuda", torch.cuda.current_device())
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(-1)).to(dev)  # noqa: E731
+        return dev, up(self._compressed, np.uint8), up(self._stream_starts, np.int64), up(self._stream_nbytes, np.int64)
+
+    @property
+    def md5(self):
+        """The STREAMINFO MD5 signature of every stream as stored: uint8, leading shape + (16,); all zero = unsigned."""
+        return stream_md5(np.asarray(self._compressed, dtype=np.uint8), self._stream_starts)
+
+    def check_md5(self, verify=None):
+        """Check the store against the MD5 signatures in its streams, with nothing but the store at hand: an int8 numpy
+        array over the leading shape, 1 = the stream decodes to the samples that were signed, 0 = it does not, -1 =
+        unsigned, -2 = not checkable (not 32 bits per sample; see check_md5_device).  The store is decoded in column
+        chunks on the device and hashed there; uses the resident store after to_device(), uploads it otherwise.
+        `verify`: the decoder's frame CRC-16 check (None = the default of set_decode_verify)."""
+        from .libflacarray import check_md5_device
+
+        _, comp, st, nb = self._device_store()
+        status = check_md5_device(comp, st, nb, self._stream_size, is_int64=self._is_int64, verify=verify)
+        return status.cpu().numpy().reshape(self._leading_shape)
+
+    def sign(self):
+        """Compute the MD5 signature of what every stream decodes to (the chunked decode-and-hash pass of check_md5) and
+        write it into the streams' STREAMINFO; returns self.  For a float store that is the quantised integers, as any
+        FLAC decoder produces them.  The store is replaced, not changed: a FlacArray(self) copy made before keeps the
+        bytes it had.  A resident store is signed on the device and only the sixteen bytes per stream travel to the host
+        mirror.  Streams that are not checkable (check_md5's -2) raise ValueError."""
+        from .libflacarray import check_md5_device, sign_streams_device
+
+        st = self._st
+        _, comp, starts, nbytes = self._device_store()
+        status, digests = check_md5_device(comp, starts, nbytes, st.samples, is_int64=st.wide, return_digests=True)
+        if bool((status == -2).any()):
+            raise ValueError("sign needs streams of 32 bits per sample with the channel count of the array's dtype")
+        blob = np.array(st.blob, dtype=np.uint8, copy=True)
+        s0 = np.asarray(st.starts, dtype=np.int64).reshape(-1)
+        blob[s0[:, None] + 26 + np.arange(16)[None, :]] = digests.cpu().numpy().reshape(-1, 16)
+        res = self._resident
+        if res is not None:
+            signed = sign_streams_device(comp.clone(), starts, digests)
+            if res.get("index") is not None:
+                res["index"].close()
+            self._resident = dict(res, compressed=signed, index=None)
+        self._st = _Store.build(st.shape, st.global_shape, st.dtype, blob, st.starts, st.nbytes_per_stream, st.offsets, st.gains, st.dist)
         return self
 
     @classmethod
-    def from_device_array(cls, data, level=5, quanta=None, precision=None, verify=None):
+    def from_device_array(cls, data, level=5, quanta=None, precision=None, verify=None, md5=None):
         """Construct a RESIDENT FlacArray from a torch tensor that already lives in HBM (int32 / int64, or float32 /
         float64 with `quanta` or `precision` as array_compress takes them): quantise + encode on the device, keep the
         store there, and mirror it to host arrays so that every property of the reference API still answers with numpy.
         Same store as from_array on the tensor's host copy; with `precision` the per-stream std is computed on the
         device (std_device) and only its n_stream values reach the host.  Integer tensors ignore quanta / precision.
         `verify`: compare the store with `data` on the device before returning (see array_compress); None = the default
-        of set_encode_verify."""
+        of set_encode_verify.  `md5`: sign the streams (see array_compress); None = the default of set_encode_md5."""
         import torch
 
         from .compress import _per_stream_quanta
@@ -515,9 +572,9 @@ class FlacArray:
                     quanta = quanta.item() if quanta.dim() == 0 else quanta.cpu().numpy()
                 lead = tuple(data.shape[:-1])
                 q = torch.from_numpy(stream_quanta(_per_stream_quanta(quanta, lead, ndt), lead, ndt)).to(data.device)
-            comp, st, nb, offsets, gains = encode(data.contiguous(), q, level=level, compact=True, precision=precision, verify=verify)
+            comp, st, nb, offsets, gains = encode(data.contiguous(), q, level=level, compact=True, precision=precision, verify=verify, md5=md5)
         elif data.dtype in (torch.int32, torch.int64):
-            comp, st, nb = encode_flac_device(data.contiguous(), level=level, compact=True, verify=verify)
+            comp, st, nb = encode_flac_device(data.contiguous(), level=level, compact=True, verify=verify, md5=md5)
         else:
             raise ValueError(f"Unsupported data type '{data.dtype}'")
         host = lambda t: None if t is None else t.cpu().numpy()  # noqa: E731
@@ -530,11 +587,11 @@ class FlacArray:
         return out
 
     @classmethod
-    def from_array(cls, arr, level=5, quanta=None, precision=None, mpi_comm=None, use_threads=False, verify=None):
-        """Construct a FlacArray from a numpy ndarray (array.py:587-637).  `verify`: see array_compress."""
+    def from_array(cls, arr, level=5, quanta=None, precision=None, mpi_comm=None, use_threads=False, verify=None, md5=None):
+        """Construct a FlacArray from a numpy ndarray (array.py:587-637).  `verify`, `md5`: see array_compress."""
         if mpi_comm is not None:
             raise NotImplementedError("mpi4py communicators are not supported; see flacarray_amd.dist")
-        pieces = array_compress(arr, level=level, quanta=quanta, precision=precision, use_threads=use_threads, verify=verify)
+        pieces = array_compress(arr, level=level, quanta=quanta, precision=precision, use_threads=use_threads, verify=verify, md5=md5)
         return cls._assemble(arr.shape, None, arr.dtype, *pieces)
 
     @classmethod

@@ -22,7 +22,7 @@ DEPS = [
 SRC_COMPACT = os.path.join(_HERE, "csrc", "compact_unit.hip")
 SRC_FUSED = os.path.join(_HERE, "csrc", "fused_unit.hip")
 SRC_PLACED = os.path.join(_HERE, "csrc", "placed_unit.hip")
-DEPS += [SRC_COMPACT, SRC_FUSED, SRC_PLACED, os.path.join(_HERE, "csrc", "encode_placed.hpp"), os.path.join(_HERE, "csrc", "encode_fused.hpp"), os.path.join(_HERE, "csrc", "verify_kernels.hpp"),
+DEPS += [SRC_COMPACT, SRC_FUSED, SRC_PLACED, os.path.join(_HERE, "csrc", "encode_placed.hpp"), os.path.join(_HERE, "csrc", "encode_fused.hpp"), os.path.join(_HERE, "csrc", "verify_kernels.hpp"), os.path.join(_HERE, "csrc", "md5_kernels.hpp"),
          os.path.join(_HERE, "csrc", "decode_latency.hpp")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared"]
 # The shipped library is built from four translation units (the fourth, the placing encoder K3G, like the first): the slot encoder and the decoder (K3, K7) with LLVM's

@@ -6,7 +6,7 @@ encoder's load for float32, in front of the two-channel encoder for float64) -- 
 """
 import numpy as np
 
-from .libflacarray import _EncodeVerify, encode_flac, encode_flac_f32, encode_flac_f64
+from .libflacarray import _EncodeMd5, _EncodeVerify, encode_flac, encode_flac_f32, encode_flac_f64
 from .utils import _quanta_for, _streams_of, function_timer
 
 _INT_KINDS = (np.dtype(np.int32), np.dtype(np.int64))
@@ -29,7 +29,7 @@ def _per_stream_quanta(quanta, leading_shape, dtype):
 
 
 @function_timer
-def array_compress(arr, level=5, quanta=None, precision=None, use_threads=False, verify=None):
+def array_compress(arr, level=5, quanta=None, precision=None, use_threads=False, verify=None, md5=None):
     """Compress a numpy array with optional floating point conversion.
 
     Integer input (int32, int64) is compressed as is and the last two elements of the result are None.
@@ -42,10 +42,14 @@ def array_compress(arr, level=5, quanta=None, precision=None, use_threads=False,
     `verify`: True = decode the streams on the device right after they are written and compare them with the input
     before returning (libFLAC's verify mode: RuntimeError on a difference; float input compares as the quantised
     integers, not the floats), False = do not, None = the default of set_encode_verify.
+
+    `md5`: True = sign every stream: the MD5 of its samples (float input: of the quantised integers, which is what any
+    FLAC decoder will produce) goes into STREAMINFO, where libFLAC writes it and `flac -t` checks it; False = leave the
+    field zero ("not computed"); None = the default of set_encode_md5.  Hashed on the device while the input is there.
     """
     if arr.size == 0:
         raise ValueError("Cannot compress a zero-sized array!")
-    with _EncodeVerify(verify):
+    with _EncodeVerify(verify), _EncodeMd5(md5):
         return _compress(arr, level, quanta, precision, use_threads)
 
 

@@ -38,6 +38,7 @@
 #include "verify_kernels.hpp"
 #include "std_kernels.hpp"
 #include "append_kernels.hpp"
+#include "md5_kernels.hpp"
 
 namespace {
 
@@ -61,9 +62,10 @@ struct DeviceState {
     std::map<int, float*> windows;  // blocksize -> device tukey(0.5) table
     uint16_t* crc_tab = nullptr;
     uint16_t* crc_tab_fused = nullptr;
-    // [10]: K1a partial ranges; [12]: std chunk sums and means, [13]: std summation plans (fa_stream_std_*_device)
-    void* scratch[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // [10]: K1a partial ranges; [12]: std chunk sums and means, [13]: std summation plans (fa_stream_std_*_device);
+    // [14]: the MD5 check's decoded column chunk, [15]: its chaining states, digests and flags (fa_check_md5_device)
+    void* scratch[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t scratch_epoch = 1;  // bumped whenever a scratch slot is (re)allocated or released: cached contents are then stale
     // frame-header table of the most recent encode geometry (host copy + what the device copy was built from)
     std::vector<uint4> h_hdr;
@@ -97,6 +99,7 @@ std::map<int, std::unique_ptr<DeviceState>> g_dev;
 std::atomic<bool> g_prof{false};
 std::atomic<bool> g_verify{false};  // fa_set_decode_verify: re-compute every decoded frame's CRC-16
 std::atomic<bool> g_encode_verify{false};  // fa_set_encode_verify: the host encoders compare each chunk's streams with its input
+std::atomic<bool> g_encode_md5{false};  // fa_set_encode_md5: the host encoders sign each chunk's streams (STREAMINFO MD5)
 
 DeviceState* dev_state() {
     int d = 0;
@@ -1003,6 +1006,11 @@ int fa_set_encode_verify(int on) {
     return was ? 1 : 0;
 }
 
+int fa_set_encode_md5(int on) {
+    const bool was = on < 0 ? g_encode_md5.load() : g_encode_md5.exchange(on != 0);
+    return was ? 1 : 0;
+}
+
 void fa_profile_enable(int on) { g_prof = (on != 0); }  // process-wide switch; the events are per device
 
 #ifdef FA_STAMPS
@@ -1042,7 +1050,7 @@ int fa_device_count(void) {
 
 void fa_release_scratch(void) {
     FA_API_LOCK_OR(return);
-    for (int i = 0; i < 14; ++i) {
+    for (int i = 0; i < 16; ++i) {
         if (ds_->scratch[i]) (void)hipFree(ds_->scratch[i]);
         ds_->scratch[i] = nullptr;
         ds_->scratch_bytes[i] = 0;
@@ -1956,6 +1964,140 @@ int fa_compare_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const i
                           stream);
 }
 
+// ---- STREAMINFO MD5: hash (K10), sign, check --------------------------------------------------------------------
+// kind 0 int32, 1 int64, 2 float32, 3 float64 rows (md5_kernels.hpp); n / row_stride / n_before in samples.  Launches in
+// stream order; d_flags (the NaN word, float kinds only) is the caller's to clear and read.
+static int md5_launch(int kind, const void* d_data, int64_t n_stream, int64_t n, int64_t row_stride, const void* d_offsets, const void* d_gains,
+                      uint32_t* d_state, int64_t n_before, int final, unsigned char* d_digest, int* d_flags, hipStream_t st) {
+    const int wd = (kind & 1) ? 2 : 1;  // dwords per sample
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(d_data);
+    const int64_t nd = n * wd, sd = row_stride * wd;
+    const uint64_t before = (uint64_t)n_before * 4u * (uint64_t)wd;
+    const bool vec = ((reinterpret_cast<uintptr_t>(d_data) & 15) == 0) && (n_stream == 1 || (sd & 3) == 0);
+    const dim3 grid((unsigned)((n_stream + 63) / 64)), block(64);
+    uint32_t* dig = reinterpret_cast<uint32_t*>(d_digest);
+#define FA_MD5_GO(K, U) \
+    hipLaunchKernelGGL((md5_rows_kernel<K, U>), grid, block, 0, st, p, n_stream, nd, sd, d_offsets, d_gains, d_state, before, final, d_state, dig, d_flags)
+    switch (kind) {
+        case 0: if (vec) FA_MD5_GO(0, 4); else FA_MD5_GO(0, 1); break;
+        case 1: if (vec) FA_MD5_GO(1, 4); else FA_MD5_GO(1, 2); break;
+        case 2: if (vec) FA_MD5_GO(2, 4); else FA_MD5_GO(2, 1); break;
+        default: if (vec) FA_MD5_GO(3, 4); else FA_MD5_GO(3, 2); break;
+    }
+#undef FA_MD5_GO
+    FA_HIP_TRY(hipGetLastError());
+    return FA_ERROR_NONE;
+}
+
+static int md5_device(int wide, const void* d_data, int64_t n_stream, int64_t n, int64_t row_stride, const void* d_offsets, const void* d_gains,
+                      uint32_t* d_state, int64_t n_before, int final, unsigned char* d_digest, void* stream) {
+    FA_API_LOCK;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    const int per_block = wide ? 8 : 16;  // samples in 64 bytes
+    if (n < 0 || n_before < 0 || (n > 0 && !d_data) || row_stride < n || (d_offsets == nullptr) != (d_gains == nullptr)) return FA_ERROR_CONVERT_TYPE;
+    if (n_before % per_block != 0 || (!final && n % per_block != 0)) return FA_ERROR_CONVERT_TYPE;  // whole 64-byte blocks before the last call
+    if ((final && !d_digest) || ((!final || n_before > 0) && !d_state)) return FA_ERROR_CONVERT_TYPE;
+    if ((reinterpret_cast<uintptr_t>(d_digest) & 15) || (reinterpret_cast<uintptr_t>(d_state) & 15)) return FA_ERROR_CONVERT_TYPE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int kind = (wide ? 1 : 0) + (d_offsets ? 2 : 0);
+    if (!d_offsets) return md5_launch(kind, d_data, n_stream, n, row_stride, nullptr, nullptr, d_state, n_before, final, d_digest, nullptr, st);
+    void* p = nullptr;
+    int rc = get_scratch(15, 256, &p);
+    if (rc) return rc;
+    int* d_flags = reinterpret_cast<int*>(p);
+    FA_HIP_TRY(hipMemsetAsync(d_flags, 0, 4, st));
+    if ((rc = md5_launch(kind, d_data, n_stream, n, row_stride, d_offsets, d_gains, d_state, n_before, final, d_digest, d_flags, st))) return rc;
+    int h = 0;
+    FA_HIP_TRY(hipMemcpyAsync(&h, d_flags, 4, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    return (h & 1) ? FA_ERROR_NAN_INPUT : FA_ERROR_NONE;
+}
+
+int fa_md5_i32_device(const void* d_data, int64_t n_stream, int64_t n, int64_t row_stride, const float* d_offsets, const float* d_gains,
+                      uint32_t* d_state, int64_t n_before, int final, unsigned char* d_digest, void* stream) {
+    return md5_device(0, d_data, n_stream, n, row_stride, d_offsets, d_gains, d_state, n_before, final, d_digest, stream);
+}
+
+int fa_md5_i64_device(const void* d_data, int64_t n_stream, int64_t n, int64_t row_stride, const double* d_offsets, const double* d_gains,
+                      uint32_t* d_state, int64_t n_before, int final, unsigned char* d_digest, void* stream) {
+    return md5_device(1, d_data, n_stream, n, row_stride, d_offsets, d_gains, d_state, n_before, final, d_digest, stream);
+}
+
+int fa_sign_streams_device(unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, int64_t n_stream, const unsigned char* d_digests,
+                           void* stream) {
+    FA_API_LOCK;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (!d_bytes || !d_starts || !d_digests || n_bytes < 0) return FA_ERROR_CONVERT_TYPE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    void* p = nullptr;
+    int rc = get_scratch(15, 256, &p);
+    if (rc) return rc;
+    int* d_flag = reinterpret_cast<int*>(p) + 1;
+    FA_HIP_TRY(hipMemsetAsync(d_flag, 0, 4, st));
+    hipLaunchKernelGGL(sign_check_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, d_bytes, n_bytes, d_starts, n_stream, d_flag);
+    int h = 0;
+    FA_HIP_TRY(hipMemcpyAsync(&h, d_flag, 4, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (h) return FA_ERROR_DECODE_INIT;  // (nothing written)
+    hipLaunchKernelGGL(sign_streams_kernel, dim3((unsigned)((n_stream * 16 + 255) / 256)), dim3(256), 0, st, d_bytes, d_starts, n_stream, d_digests);
+    FA_HIP_TRY(hipGetLastError());
+    return FA_ERROR_NONE;
+}
+
+int fa_check_md5_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                        int64_t stream_size, int channels, int64_t max_temp_bytes, int8_t* d_status, unsigned char* d_digests, void* stream,
+                        int verify) {
+    FA_API_LOCK;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
+    if (!d_bytes || !d_starts || !d_nbytes || !d_status || (channels != 1 && channels != 2)) return FA_ERROR_CONVERT_TYPE;
+    if (reinterpret_cast<uintptr_t>(d_digests) & 15) return FA_ERROR_CONVERT_TYPE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // [15]: flags and counts (256 bytes) | chaining states | digests (when the caller wants none)
+    void* p = nullptr;
+    int rc = get_scratch(15, 256 + (size_t)n_stream * 32, &p);
+    if (rc) return rc;
+    int* d_counts = reinterpret_cast<int*>(p) + 2;
+    uint32_t* d_state = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(p) + 256);
+    unsigned char* d_dig = d_digests ? d_digests : reinterpret_cast<unsigned char*>(d_state + 4 * n_stream);
+    FA_HIP_TRY(hipMemsetAsync(d_counts, 0, 8, st));
+    const dim3 sgrid((unsigned)((n_stream + 255) / 256));
+    hipLaunchKernelGGL(md5_classify_kernel, sgrid, dim3(256), 0, st, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, channels, d_status, d_counts);
+    int h_counts[2] = {0, 0};
+    FA_HIP_TRY(hipMemcpyAsync(h_counts, d_counts, 8, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (d_digests) FA_HIP_TRY(hipMemsetAsync(d_digests, 0, (size_t)n_stream * 16, st));
+    // nothing to decide (and no digest asked for that a decode could give): the store is not decoded
+    if (h_counts[0] == 0 && !(d_digests && h_counts[1] > 0)) return FA_ERROR_NONE;
+    // column chunks: whole 64-byte blocks of every stream, the decoded chunk under the cap
+    const int64_t per_block = channels == 2 ? 8 : 16;
+    const int64_t sample_bytes = 4 * channels;
+    const int64_t cap = max_temp_bytes > 0 ? max_temp_bytes : (int64_t)FA_MD5_CHECK_TEMP_BYTES;
+    int64_t width = cap / (n_stream * sample_bytes) / per_block * per_block;
+    if (width < per_block) width = per_block;
+    if (width > stream_size) width = stream_size;
+    void* d_tmp = nullptr;
+    if ((rc = get_scratch(14, (size_t)n_stream * (size_t)width * (size_t)sample_bytes + 256, &d_tmp))) return rc;
+    for (int64_t at = 0; at < stream_size; at += width) {
+        const int64_t w = std::min(width, stream_size - at);
+        const bool whole = (w == stream_size);
+        const int64_t first = whole ? -1 : at, last = whole ? -1 : at + w;
+        rc = channels == 2 ? fa_decode_i64_device(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last,
+                                                  reinterpret_cast<int64_t*>(d_tmp), nullptr, nullptr, nullptr, stream, verify)
+                           : fa_decode_i32_device(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last,
+                                                  reinterpret_cast<int32_t*>(d_tmp), nullptr, nullptr, nullptr, stream, verify);
+        if (rc) return rc;
+        if ((rc = md5_launch(channels == 2 ? 1 : 0, d_tmp, n_stream, w, w, nullptr, nullptr, d_state, at, at + w == stream_size, d_dig, nullptr, st)))
+            return rc;
+    }
+    hipLaunchKernelGGL(md5_compare_kernel, sgrid, dim3(256), 0, st, d_bytes, d_starts, n_stream, d_dig, d_status);
+    FA_HIP_TRY(hipStreamSynchronize(st));  // (the scratch is free again, d_status / d_digests are complete)
+    FA_HIP_TRY(hipGetLastError());
+    return FA_ERROR_NONE;
+}
+
 int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t stream_size, const float* d_quanta,
                                int32_t* d_output, float* d_offsets, float* d_gains, void* stream) {
     FA_API_LOCK;
@@ -2154,11 +2296,12 @@ struct Feeder {
     ~Feeder() { finish(); }
 };
 
-static int64_t host_chunk_streams(int64_t n_stream, size_t bytes_per_stream, int64_t max_by_grid) {
+static int64_t host_chunk_streams(int64_t n_stream, size_t bytes_per_stream, int64_t max_by_grid, bool signing = false) {
     // ~256 MiB per chunk, at least 8 chunks for arrays that can afford them (the first upload and the last download are
-    // not overlapped with anything), never more than the grid allows
+    // not overlapped with anything), never more than the grid allows.  Signing: the MD5 of a chunk takes the time of ONE
+    // stream's chain however many streams the chunk holds (md5_kernels.hpp), once per chunk -- so fewer, larger chunks.
     const size_t total = (size_t)n_stream * bytes_per_stream;
-    size_t target = 256u << 20;
+    size_t target = signing ? ((size_t)2048u << 20) : ((size_t)256u << 20);
     if (total / 8 < target) target = total / 8 > (32u << 20) ? total / 8 : (32u << 20);
     if (const char* e = std::getenv("FLACARRAY_HIP_HOST_CHUNK_BYTES")) {  // tests: many small chunks through the pipeline
         const long long v = std::atoll(e);
@@ -2198,8 +2341,9 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     const unsigned char* data = reinterpret_cast<const unsigned char*>(data_v);
     const size_t stream_bytes = (size_t)stream_size * 4 * (size_t)nch;
     const bool verifying = g_encode_verify.load();
+    const bool signing = g_encode_md5.load();
     // (verifying two-channel chunks also takes the decoder's planar image, as large again as the chunk's input)
-    const int64_t chunk = host_chunk_streams(n_stream, stream_bytes * (verifying && nch == 2 ? 2 : 1), 0x7fffffffLL / one.nf);
+    const int64_t chunk = host_chunk_streams(n_stream, stream_bytes * (verifying && nch == 2 ? 2 : 1), 0x7fffffffLL / one.nf, signing);
     const int64_t n_chunks = (n_stream + chunk - 1) / chunk;
     const bool fused_f32 = f32 && fused_geometry(chunk, stream_size, level, true) &&
                            (n_stream % chunk == 0 || fused_geometry(n_stream % chunk, stream_size, level, true));
@@ -2212,7 +2356,7 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     const int64_t wsb = single_pass_workspace_for(chunk, stream_size, level, nch);  // (the slot sequence's size when that is forced)
     if (wsb < 0) return FA_ERROR_ENCODE_PROCESS;
     if ((rc = get_scratch(5, (size_t)wsb, &d_ws))) return rc;
-    if ((rc = get_scratch(4, (size_t)chunk * 48 + 1024, &d_aux))) return rc;
+    if ((rc = get_scratch(4, (size_t)chunk * 64 + 1024, &d_aux))) return rc;
     int64_t* d_starts = reinterpret_cast<int64_t*>(d_aux);
     int64_t* d_nb = d_starts + chunk;
     float* d_q = reinterpret_cast<float*>(d_nb + chunk);
@@ -2222,6 +2366,7 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     double* d_off64 = d_q64 + chunk;
     double* d_gain64 = d_off64 + chunk;
     int64_t* d_mm = reinterpret_cast<int64_t*>(d_gain64 + chunk);  // encode verification: first mismatch per stream
+    unsigned char* d_dig = reinterpret_cast<unsigned char*>(d_mm + chunk);  // signing: the chunk's digests (16-byte aligned: d_aux is, chunk * 48 is)
     std::vector<int64_t> h_mm(verifying ? (size_t)chunk : 0);
     const int64_t cap_chunk = capacity_bytes_for(chunk, stream_size, level, nch);
     if ((rc = get_scratch(3, (size_t)cap_chunk + 256, &d_out))) return rc;
@@ -2311,6 +2456,18 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
                 if (h_mm[i] >= 0) err = FA_ERROR_ENCODE_VERIFY;
             if (err & (FA_ERROR_DECODE_INIT | FA_ERROR_DECODE_PROCESS | FA_ERROR_DECODE_SEEK))
                 err = FA_ERROR_ENCODE_VERIFY;  // (a stream the decoder cannot read back is a failed verification)
+            if (err) break;
+        }
+        if (signing) {
+            // the STREAMINFO MD5 of the chunk's integers, hashed from the input slot while it is still there (float input is
+            // quantised where it is loaded, with the offsets / gains the encoder used) and patched into the chunk's blob
+            // before it goes down
+            const void *soff = nullptr, *sgain = nullptr;
+            if (f32) { soff = d_off; sgain = d_gain; }
+            if (f64) { soff = d_off64; sgain = d_gain64; }
+            err = md5_device(nch == 2, d_in, ns, stream_size, stream_size, soff, sgain, nullptr, 0, 1, d_dig, nullptr);
+            if (!err) err = fa_sign_streams_device(reinterpret_cast<unsigned char*>(d_out), total, d_starts, ns, d_dig, nullptr);
+            if (!err && hipStreamSynchronize(nullptr) != hipSuccess) err = FA_ERROR_DEVICE;
             if (err) break;
         }
         if (n_chunks > 1) {

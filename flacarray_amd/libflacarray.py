@@ -221,6 +221,44 @@ class _EncodeVerify:
         return False
 
 
+_encode_md5_lock = threading.Lock()
+
+
+def set_encode_md5(on):
+    """Process-wide DEFAULT of STREAMINFO MD5 signing, used by every encode call whose `md5` argument is None: when on,
+    the MD5 of each stream's integers (int32: the row's bytes; int64: the same, channel 0 = low word; float input: the
+    integers it is quantised to, which is what any FLAC decoder will produce) is computed on the device and written
+    into bytes [26, 42) of the stream, where libFLAC writes it and `flac -t` checks it.  Off, the field holds sixteen
+    zero bytes ("not computed").  Returns the previous setting; initially off.  Callers of the reference's C entry
+    points (encode_i32, encode_i64, ...) get signing through this default alone (fa_set_encode_md5)."""
+    with _encode_md5_lock:
+        return bool(_lib.lib().fa_set_encode_md5(1 if on else 0))
+
+
+def _encode_md5_default():
+    return bool(_lib.lib().fa_set_encode_md5(-1))
+
+
+class _EncodeMd5:
+    """Hold the library's encode-md5 setting at `md5` for one host encode call (None: the default as it is); the twin
+    of _EncodeVerify, always entered after it."""
+
+    def __init__(self, md5):
+        self.md5 = md5
+
+    def __enter__(self):
+        if self.md5 is not None:
+            _encode_md5_lock.acquire()
+            self.prev = _lib.lib().fa_set_encode_md5(1 if self.md5 else 0)
+        return self
+
+    def __exit__(self, *exc):
+        if self.md5 is not None:
+            _lib.lib().fa_set_encode_md5(self.prev)
+            _encode_md5_lock.release()
+        return False
+
+
 def _check_encode(errcode):
     if errcode & _lib.ERROR_NAN_INPUT:
         raise RuntimeError("Cannot convert data with NaNs to integers")
@@ -390,13 +428,15 @@ def wrap_encode_i64_threaded(flatdata, n_stream, stream_size, level):
 
 
 
-def encode_flac(data, level, use_threads=False, verify=None):
+def encode_flac(data, level, use_threads=False, verify=None, md5=None):
     """Compress an integer array to FLAC streams (libflacarray.pyx:529-594).
 
     Returns (compressed bytestream, stream starting bytes, stream nbytes); starts and nbytes
     have the leading shape of `data` and are at least 1-D.  `verify`: True = decode what was written, on the device,
     and compare it with the input before returning (libFLAC's verify mode; a difference raises RuntimeError), False =
-    do not, None = the default of set_encode_verify.
+    do not, None = the default of set_encode_verify.  `md5`: True = sign every stream (the MD5 of its samples in
+    STREAMINFO, computed on the device while the input is there), False = leave the field zero, None = the default of
+    set_encode_md5.
     """
     if data.dtype != flac_i32_dtype and data.dtype != flac_i64_dtype:
         raise RuntimeError("Only 32bit or 64bit integer data is supported")
@@ -417,7 +457,7 @@ def encode_flac(data, level, use_threads=False, verify=None):
         enc = wrap_encode_i64_threaded if use_threads else wrap_encode_i64
     else:
         enc = wrap_encode_i32_threaded if use_threads else wrap_encode_i32
-    with _EncodeVerify(verify):
+    with _EncodeVerify(verify), _EncodeMd5(md5):
         compressed, flatstarts, flatnbytes = enc(flatdata, n_stream, stream_size, level)
     return (compressed, flatstarts.reshape(starts_shape), flatnbytes.reshape(starts_shape))
 
@@ -564,7 +604,7 @@ class EncodeWorkspace:
         return self.buf
 
 
-def encode_flac_device(data, level=5, workspace=None, return_info=False, compact=False, capacity_bytes=None, verify=False):
+def encode_flac_device(data, level=5, workspace=None, return_info=False, compact=False, capacity_bytes=None, verify=False, md5=None):
     """Encode a C-contiguous int32 (or int64: two-channel streams) CUDA tensor [..., stream_size] held in HBM.
 
     Returns (compressed uint8 tensor, starts int64 tensor, nbytes int64 tensor), all on the
@@ -582,10 +622,16 @@ def encode_flac_device(data, level=5, workspace=None, return_info=False, compact
     `verify=True`: the streams are decoded and compared with `data` on the device before the call returns
     (compare_flac_device); a difference raises RuntimeError naming the first differing stream(s) and sample.  The
     returned bytes are the same either way.
+
+    `md5`: True = sign the streams (md5_device over `data`, patched into STREAMINFO by sign_streams_device: sixteen
+    bytes per stream, every other byte as without it), False = leave the field zero, None = the default of
+    set_encode_md5.
     """
     out = _encode_flac_device(data, level, workspace, return_info, compact, capacity_bytes)
     if verify:
         _raise_on_mismatch(compare_flac_device(out[0], out[1], out[2], data))
+    if _encode_md5_default() if md5 is None else md5:
+        sign_streams_device(out[0], out[1], md5_device(data))
     return out
 
 
@@ -708,7 +754,7 @@ def _precision_quanta_device(data, precision):
     return torch.from_numpy(q).to(data.device)
 
 
-def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=False, precision=None, verify=False):
+def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=False, precision=None, verify=False, md5=None):
     """Quantise and encode a C-contiguous float32 CUDA tensor [..., stream_size] held in HBM: the device-resident
     analogue of array_compress on float32 input (compress.py:50-84 -> float_to_int + encode_flac).
 
@@ -719,10 +765,13 @@ def encode_flac_device_f32(data, quanta=None, level=5, workspace=None, compact=F
     run one after the other.  Same bytes, offsets and gains either way.  `precision` p (instead of `quanta`): quanta =
     std / 10^p per stream as array_compress derives them (std_device, then the host path's numpy expression).
     `verify=True`: compare the streams with `data` before returning, as encode_flac_device does -- the quantised integers,
-    not the floats."""
+    not the floats.  `md5`: sign the streams (None = the default of set_encode_md5) with the MD5 of the quantised
+    integers -- hashed from the floats, quantised where they are loaded: the integers need not exist."""
     out = _encode_flac_device_f32(data, quanta, level, workspace, compact, precision)
     if verify:
         _raise_on_mismatch(compare_flac_device(out[0], out[1], out[2], data, out[3], out[4]))
+    if _encode_md5_default() if md5 is None else md5:
+        sign_streams_device(out[0], out[1], md5_device(data, out[3], out[4]))
     return out
 
 
@@ -750,7 +799,7 @@ def _encode_flac_device_f32(data, quanta, level, workspace, compact, precision):
     # (the fused kernel, K3F, takes levels 3-8 only: levels 0-2 of any length quantise first, then go to K3G)
     if not (level >= 3 and data.data_ptr() % 16 == 0 and stream_size % 4096 == 0 and L.fa_encode_single_pass_supported(n_stream, stream_size, level)):
         ints, offsets, gains = float32_to_int32_device(data, q)
-        comp, st, nb = encode_flac_device(ints, level=level, workspace=workspace, compact=compact)
+        comp, st, nb = encode_flac_device(ints, level=level, workspace=workspace, compact=compact, md5=False)
         return comp, st, nb, offsets, gains
     if workspace is None:
         workspace = EncodeWorkspace()
@@ -777,14 +826,15 @@ def _encode_flac_device_f32(data, quanta, level, workspace, compact, precision):
     return compressed, starts.reshape(lead), nbytes.reshape(lead), offsets.reshape(lead), gains.reshape(lead)
 
 
-def encode_flac_device_f64(data, quanta=None, level=5, workspace=None, compact=False, precision=None, verify=False):
+def encode_flac_device_f64(data, quanta=None, level=5, workspace=None, compact=False, precision=None, verify=False, md5=None):
     """Quantise and encode a C-contiguous float64 CUDA tensor [..., stream_size] held in HBM: the device-resident
     analogue of array_compress on float64 input (float64_to_int64, then the two-channel encoder).
 
     `quanta`: None (per-stream quanta from the data range) or a tensor with one value per stream; `precision` p
     instead: quanta = std / 10^p per stream, as for encode_flac_device_f32.  Returns (compressed, starts, nbytes,
     offsets, gains), offsets / gains float64 with the leading shape of `data`.  `verify=True`: compare the streams with
-    `data` before returning (the quantised integers, not the floats)."""
+    `data` before returning (the quantised integers, not the floats).  `md5`: sign the streams with the MD5 of the
+    quantised integers (None = the default of set_encode_md5)."""
     torch = _torch()
     if data.dtype != torch.float64 or not data.is_contiguous():
         raise ValueError("Only float32 and float64 data are supported")
@@ -797,7 +847,7 @@ def encode_flac_device_f64(data, quanta=None, level=5, workspace=None, compact=F
             raise RuntimeError("Cannot set both quanta and precision")
         quanta = _precision_quanta_device(data, precision)
     ints, offsets, gains = float64_to_int64_device(data, quanta)
-    comp, st, nb = encode_flac_device(ints, level=level, workspace=workspace, compact=compact)
+    comp, st, nb = encode_flac_device(ints, level=level, workspace=workspace, compact=compact, md5=md5)
     if verify:
         _raise_on_mismatch(compare_flac_device(comp, st, nb, data, offsets, gains))
     return comp, st, nb, offsets, gains
@@ -872,6 +922,161 @@ def compare_flac_device(compressed, starts, nbytes, data, offsets=None, gains=No
     if errcode != 0:
         raise RuntimeError(f"Comparison failed, return code = {errcode}")
     return first
+
+
+def md5_device(data, offsets=None, gains=None, state=None, n_before=0, final=True):
+    """MD5 of every stream of a device tensor [..., stream_size], one GPU lane per stream (fa_md5_i32_device /
+    fa_md5_i64_device): a uint8 tensor of shape (n_stream, 16), equal to hashlib.md5 of each row's little-endian bytes --
+    which is what libFLAC writes into STREAMINFO for the 32-bit one-channel (int32) and two-channel (int64) streams of
+    this library.
+
+    `data`: int32 or int64, or float32 / float64 with `offsets` and `gains` (one value per stream): the floats are
+    quantised where they are loaded, exactly as the encoder quantises them, and the hash is that of the integers (a NaN
+    raises RuntimeError).  C-contiguous, or a 2-D column range of a wider C-contiguous image (unit stride along the
+    stream, any row stride).  A stream of length 0 gives the digest of the empty message.
+
+    Resumable: `final=False` hashes a whole number of 64-byte blocks (a multiple of 16 int32 / 8 int64 samples) and
+    returns the chaining state, an int32 tensor (n_stream, 4), instead of the digest; the next call passes it as `state`
+    together with `n_before`, the samples of every stream hashed so far.  The last call (`final=True`) adds the padding
+    and the length of all n_before + stream_size samples."""
+    torch = _torch()
+    if data.dtype not in (torch.int32, torch.int64, torch.float32, torch.float64):
+        raise ValueError(f"Unsupported data type '{data.dtype}': int32, int64, float32 or float64")
+    if data.dim() == 0:
+        raise ValueError("data needs a stream axis")
+    n = int(data.shape[-1])
+    n_stream = int(np.prod(data.shape[:-1])) if data.dim() > 1 else 1
+    if n_stream <= 0:
+        raise ValueError("data needs at least one stream")
+    stride = n
+    if data.dim() == 2 and not data.is_contiguous():
+        if (n > 1 and data.stride(1) != 1) or (n_stream > 1 and data.stride(0) < n):
+            raise ValueError("Only C-contiguous data, or a column range of a C-contiguous 2-D array, is supported")
+        stride = int(data.stride(0)) if n_stream > 1 else n
+    elif not data.is_contiguous():
+        raise ValueError("Only C-contiguous data, or a column range of a C-contiguous 2-D array, is supported")
+    is_float = data.dtype in (torch.float32, torch.float64)
+    if (offsets is None) != (gains is None):
+        raise ValueError("When specifying offsets, you must also provide the gains")
+    if is_float and offsets is None:
+        raise ValueError("Hashing float data needs the offsets and gains that quantise it")
+    if not is_float and offsets is not None:
+        raise ValueError("offsets and gains apply to float data only")
+    if is_float and (offsets.numel() != n_stream or gains.numel() != n_stream):
+        raise ValueError("offsets and gains need one value per stream")
+    wide = data.dtype in (torch.int64, torch.float64)
+    per_block = 8 if wide else 16
+    if n_before < 0 or n_before % per_block != 0:
+        raise ValueError(f"n_before must be a whole number of 64-byte blocks ({per_block} samples)")
+    if not final and n % per_block != 0:
+        raise ValueError(f"A call that is not the last must hash a whole number of 64-byte blocks ({per_block} samples)")
+    if (n_before > 0) != (state is not None):
+        raise ValueError("state and n_before go together: both from the previous call, or neither")
+    if state is not None and (state.dtype != torch.int32 or tuple(state.shape) != (n_stream, 4) or not state.is_contiguous()):
+        raise ValueError("state must be the int32 tensor of shape (n_stream, 4) a call with final=False returned")
+    if not data.is_cuda:
+        raise RuntimeError("md5_device needs a tensor on the GPU")
+    dev = data.device
+    if state is not None and state.device != dev:
+        raise RuntimeError("md5_device needs state on the GPU of data")
+    if is_float:
+        offsets = offsets.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+        gains = gains.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+    digest = torch.empty((n_stream, 16), dtype=torch.uint8, device=dev) if final else None
+    if not final:
+        state = state.clone() if state is not None else torch.empty((n_stream, 4), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    with _on_device(dev):
+        errcode = (L.fa_md5_i64_device if wide else L.fa_md5_i32_device)(
+            _dp(data), n_stream, n, stride, _dp(offsets), _dp(gains), _dp(state), n_before, 1 if final else 0, _dp(digest), _stream_ptr())
+    if errcode & _lib.ERROR_NAN_INPUT:
+        raise RuntimeError("Cannot convert data with NaNs to integers")
+    if errcode != 0:
+        raise RuntimeError(f"MD5 failed, return code = {errcode}")
+    return digest if final else state
+
+
+def sign_streams_device(compressed, starts, digests):
+    """Write `digests` (uint8, sixteen bytes per stream, as md5_device returns them) into the MD5 field of every
+    stream's STREAMINFO, bytes [start + 26, start + 42), IN PLACE on the device; returns `compressed`.  Raises
+    ValueError, with nothing written, if a stream does not begin with "fLaC" and a STREAMINFO block."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8 or digests.dtype != torch.uint8:
+        raise ValueError("compressed and digests should be of type uint8")
+    if starts.dtype != torch.int64:
+        raise ValueError("starts should be of type int64")
+    n_stream = int(np.prod(starts.shape))
+    if digests.numel() != 16 * n_stream:
+        raise ValueError("digests need sixteen bytes per stream")
+    if not (compressed.is_contiguous() and starts.is_contiguous() and digests.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and digests.device == dev):
+        raise RuntimeError("sign_streams_device needs compressed, starts and digests on the same GPU")
+    with _on_device(dev):
+        errcode = _lib.lib().fa_sign_streams_device(_dp(compressed), compressed.numel(), _dp(starts), n_stream, _dp(digests), _stream_ptr())
+    if errcode == 8192:  # FA_ERROR_DECODE_INIT
+        raise ValueError("Signing needs streams that start with fLaC and a STREAMINFO block inside the compressed bytes")
+    if errcode != 0:
+        raise RuntimeError(f"Signing failed, return code = {errcode}")
+    return compressed
+
+
+def check_md5_device(compressed, starts, nbytes, stream_size, is_int64=False, return_digests=False, verify=None, max_temp_bytes=None):
+    """Check device-resident streams against the MD5 signature in their STREAMINFO -- the end-to-end check of `flac -t`,
+    the only one in the format that does not depend on the bitstream: the store is decoded in column chunks (each a
+    whole number of 64-byte blocks, the decoded chunk under `max_temp_bytes`, default 256 MiB), every chunk is hashed
+    by the resumable md5 kernel, and the digests are compared with the stored ones (fa_check_md5_device).
+
+    Returns an int8 tensor of the shape of `starts`: 1 = the stream decodes to the samples that were signed, 0 = it
+    does not, -1 = unsigned (the field is zero: every store written with signing off), -2 = not checkable: not 32 bits
+    per sample (libFLAC hashes those at ceil(bps / 8) bytes per sample; they decode here to int32), or not the channel
+    count of the call (is_int64: two).  With `return_digests` also the computed digests, uint8 of shape starts.shape +
+    (16,) (zero for -2).  A store with nothing to decide is not decoded.  `verify`: the decoder's frame CRC-16 check, as
+    decode_flac_device takes it; decode errors raise RuntimeError as there.  Streams of several block sizes are checked
+    one block size at a time; with more than one column chunk each of these needs a single block size, as ranged decodes do."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64:
+        raise ValueError("starts and nbytes should be of type int64")
+    if starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes must have the same shape")
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    if stream_size <= 0:
+        raise ValueError("You must specify the non-zero stream size")
+    n_stream = int(np.prod(starts.shape))
+    if n_stream <= 0:
+        raise ValueError("starts needs at least one stream")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("check_md5_device needs compressed, starts and nbytes on the same GPU")
+    status = torch.empty(n_stream, dtype=torch.int8, device=dev)
+    digests = torch.empty((n_stream, 16), dtype=torch.uint8, device=dev) if return_digests else None
+    cap = 0 if max_temp_bytes is None else int(max_temp_bytes)
+    with _on_device(dev):
+        errcode = _lib.lib().fa_check_md5_device(
+            _dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, 2 if is_int64 else 1, cap,
+            _dp(status), _dp(digests), _stream_ptr(), _verify_arg(verify))
+    if errcode != 0:
+        # streams of different block sizes: one call per block size (see _blocksize_classes), rows scattered back
+        st, nb = starts.reshape(-1), nbytes.reshape(-1)
+        groups = None
+        if n_stream > 1 and bool(((st >= 0) & (nb >= 12) & (st + nb <= compressed.numel())).all()):
+            groups = _blocksize_classes(compressed[st[:, None] + torch.arange(12, device=dev)[None, :]].cpu().numpy())
+        if groups is None:
+            raise RuntimeError(f"Decoding failed, return code = {errcode}")
+        for g in groups:
+            gi = torch.from_numpy(g).to(dev)
+            part = check_md5_device(compressed, st[gi].contiguous(), nb[gi].contiguous(), stream_size, is_int64=is_int64,
+                                    return_digests=return_digests, verify=verify, max_temp_bytes=max_temp_bytes)
+            if return_digests:
+                status[gi], digests[gi] = part
+            else:
+                status[gi] = part
+    status = status.reshape(starts.shape)
+    return (status, digests.reshape(tuple(starts.shape) + (16,))) if return_digests else status
 
 
 def _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, is_int64):
@@ -1177,7 +1382,8 @@ def float64_to_int64_device(data, quanta=None):
     return out, offsets.reshape(lead), gains.reshape(lead)
 
 
-def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, offsets=None, gains=None, verify=False, compact=False):
+def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, offsets=None, gains=None, verify=False, compact=False,
+                       md5=False):
     """Extend every stream of a device-resident store by data.shape[-1] samples: returns the new (compressed, starts,
     nbytes), all on the device, the store's arguments left as they are.
 
@@ -1192,7 +1398,11 @@ def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, o
     encode_flac_device does.  A store whose STREAMINFO names another block size, channel count (one for int32 / float32
     data, two for int64 / float64) or stream size than the call's raises ValueError before anything is decoded.
     `verify=True`: decode the re-encoded span, samples [stream_size - r, stream_size + n) (r = the old short tail), and
-    compare it with the old tail and the new integers; a difference raises RuntimeError."""
+    compare it with the old tail and the new integers; a difference raises RuntimeError.
+
+    The splice writes a fresh stream header, so the result is UNSIGNED (MD5 field zero) whatever the old store was: a
+    finished digest cannot be resumed.  `md5=True` signs it, at the cost of one decode of the whole new store
+    (check_md5_device's chunked pass); explicit only -- it does not follow set_encode_md5."""
     torch = _torch()
     if compressed.dtype != torch.uint8:
         raise ValueError("Compressed data should be of type uint8")
@@ -1268,4 +1478,7 @@ def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, o
         if bool(bad.any()):
             first = torch.where(bad, (span != want).int().argmax(dim=1) + lo, torch.full_like(bad, -1, dtype=torch.int64))
             _raise_on_mismatch(first)
+    if md5:
+        _, digests = check_md5_device(out[0], out[1], out[2], stream_size + n, is_int64=wide, return_digests=True)
+        sign_streams_device(out[0], out[1], digests)
     return out

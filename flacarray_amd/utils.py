@@ -161,3 +161,25 @@ def select_keep_indices(arr, indices):
     if len(indices) == 0:
         return np.zeros(0, dtype=arr.dtype)
     return np.array(arr[tuple(np.array(indices).T)], dtype=arr.dtype)
+
+
+def stream_md5(compressed, stream_starts):
+    """The STREAMINFO MD5 signature of every stream, read from the bytes (no device): a uint8 array of shape
+    stream_starts.shape + (16,).  Sixteen zero bytes mean "not computed" (what this library writes unless signing is
+    on, see set_encode_md5); anything else is the MD5 of the stream's samples as libFLAC hashes them -- interleaved,
+    little-endian, ceil(bits per sample / 8) bytes each.  Raises ValueError for a stream that does not start with
+    "fLaC" and a STREAMINFO block inside `compressed`."""
+    blob = np.asarray(compressed)
+    if blob.dtype != np.uint8 or blob.ndim != 1:
+        raise ValueError("Compressed data should be a 1-D array of type uint8")
+    starts = np.asarray(stream_starts, dtype=np.int64)
+    flat = starts.reshape(-1)
+    if np.any(flat < 0) or np.any(flat + 42 > blob.size):
+        raise ValueError("A stream start lies outside the compressed bytes (or leaves no room for STREAMINFO)")
+    head = blob[flat[:, None] + np.arange(42)[None, :]]
+    # "fLaC", then the first metadata block: type 0 (the last-block flag aside), length 34
+    ok = np.all(head[:, 0:4] == np.frombuffer(b"fLaC", np.uint8), axis=1) & ((head[:, 4] & 0x7F) == 0)
+    ok &= (head[:, 5] == 0) & (head[:, 6] == 0) & (head[:, 7] == 34)
+    if not np.all(ok):
+        raise ValueError(f"Stream {int(np.flatnonzero(~ok)[0])} does not start with fLaC and a STREAMINFO block")
+    return np.ascontiguousarray(head[:, 26:42]).reshape(starts.shape + (16,))

@@ -280,6 +280,54 @@ int fa_set_decode_verify(int on);
  * returns the setting and leaves it); initially off. */
 int fa_set_encode_verify(int on);
 
+/* ---- STREAMINFO MD5: the signature libFLAC writes into every stream (the MD5 of the samples it encodes, interleaved,
+ * little-endian) and `flac -t` checks.  For the streams of this library -- 32 bits per sample, one channel (int32) or two
+ * (int64: channel 0 = low word) -- the message is exactly the bytes of the integer row.  The encoders write sixteen zero
+ * bytes ("not computed") unless signing is asked for; no encode, header or splice kernel knows about it: a signature is
+ * computed by fa_md5_*_device and patched in by fa_sign_streams_device. ---- */
+
+/* MD5 of every row of a device image, one lane per stream: d_data[s * row_stride + i], i < n, is int32 (fa_md5_i32_device)
+ * or int64 (fa_md5_i64_device) -- or, when d_offsets / d_gains [n_stream] are given, float32 / float64 quantised with them
+ * where it is loaded, exactly as the encoder quantises (FA_ERROR_NAN_INPUT for a NaN) -- so the signature of float input
+ * is that of the integers any FLAC decoder will produce.  row_stride >= n (in elements) lets a column range of a wider
+ * image be hashed.  Resumable: d_state[n_stream][4] is the per-stream chaining state, n_before the samples of every stream
+ * hashed by earlier calls.  A call with final == 0 hashes a whole number of 64-byte blocks (n a multiple of 16 for int32 /
+ * float32, of 8 for int64 / float64; FA_ERROR_CONVERT_TYPE otherwise) and writes d_state; the call with final != 0 (any n,
+ * 0 included) hashes the padding and the bit length of all n_before + n samples and writes d_digest[n_stream][16].  d_state
+ * is read only when n_before > 0 and may be NULL for a one-call hash; d_state and d_digest are 16-byte aligned.  Stream
+ * order, no wait on the stream -- except for float input (one wait, for the NaN word). */
+int fa_md5_i32_device(const void* d_data, int64_t n_stream, int64_t n, int64_t row_stride, const float* d_offsets, const float* d_gains,
+                      uint32_t* d_state, int64_t n_before, int final, unsigned char* d_digest, void* stream);
+int fa_md5_i64_device(const void* d_data, int64_t n_stream, int64_t n, int64_t row_stride, const double* d_offsets, const double* d_gains,
+                      uint32_t* d_state, int64_t n_before, int final, unsigned char* d_digest, void* stream);
+
+/* Sign: write d_digests[s][16] into bytes [d_starts[s] + 26, d_starts[s] + 42) of d_bytes, the MD5 field of STREAMINFO.
+ * Every stream must begin with "fLaC" and a STREAMINFO block inside d_bytes[0, n_bytes): FA_ERROR_DECODE_INIT otherwise,
+ * and nothing is written.  Waits on the stream once (for that check); the patch itself is in stream order. */
+int fa_sign_streams_device(unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, int64_t n_stream, const unsigned char* d_digests,
+                           void* stream);
+
+/* Check: decode the store (channels = 1: fa_decode_i32_device, 2: fa_decode_i64_device; `verify` and the error bits are
+ * theirs) in column chunks of whole 64-byte blocks, each chunk hashed with the resumable kernel, and compare every stream's
+ * digest with its STREAMINFO.  The decoded chunk -- the only large temporary -- stays under max_temp_bytes
+ * (<= 0: FA_MD5_CHECK_TEMP_BYTES) unless one 64-byte block of every stream is more.  d_status[n_stream] (int8) receives
+ * 1 = match, 0 = mismatch, -1 = unsigned (the field is all zero), -2 = not checkable: no STREAMINFO at the stream's start,
+ * another channel count than `channels`, or not 32 bits per sample (libFLAC hashes those at ceil(bps / 8) bytes per sample;
+ * this library decodes them to int32).  d_digests (may be NULL; 16-byte aligned) receives the computed digests [n_stream][16]
+ * of the streams of status 1, 0 and -1.  A store without any stream to decide (and no digest asked for) is not decoded.
+ * With more than one chunk the streams must share one block size, as every ranged decode needs.  Synchronises the stream. */
+#define FA_MD5_CHECK_TEMP_BYTES (256LL << 20)
+int fa_check_md5_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                        int64_t stream_size, int channels, int64_t max_temp_bytes, int8_t* d_status, unsigned char* d_digests, void* stream,
+                        int verify);
+
+/* Sign while encoding: when on, the host-pointer encoders (encode_i32[_threaded], encode_i64[_threaded], fa_encode_f32_host,
+ * fa_encode_f64_host -- their argument lists are the reference's and cannot grow) hash every chunk of streams on the device
+ * while its input is still there and patch the digests into the chunk's bytes before they go back to the host.
+ * Process-wide; returns the previous setting (on < 0: returns the setting and leaves it); initially off, and with it off
+ * every byte written is what it was before this entry point existed. */
+int fa_set_encode_md5(int on);
+
 /* Compare device-resident streams with the samples they should decode to, without writing the decoded samples anywhere:
  * d_first_mismatch[n_stream] (device) receives, per stream, the index of the first sample that differs, or -1.  What is
  * compared is integers: d_data is int32 for fa_compare_i32_device and int64 for fa_compare_i64_device, or -- when
