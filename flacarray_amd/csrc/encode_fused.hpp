@@ -63,6 +63,24 @@ constexpr int kFCrcXpow = 520;                                  // x^(8 (i - 255
 #ifndef FA_F_BFLY_N
 #define FA_F_BFLY_N 1  // the nine lag sums step by step side by side (one LDS round trip for all swizzles) instead of one after the other
 #endif
+#ifndef FA_F_SHLEV
+#define FA_F_SHLEV 1  // one wave of the workgroup solves the LPC problems (Levinson-Durbin, order choice, coefficient quantisation) of all
+                      // four frames side by side, 16 lanes per frame, and the FIXED analysis runs behind the lag products, so that
+                      // nobody waits for the solve: hand-over through LDS with an arrival counter and ready flags, no barrier.
+                      // 0: every wave solves its own problem, FIXED analysis first (the form up to round 4).  A first shared form
+                      // with two workgroup barriers saved the same instructions and ran 2.5 % slower (profiles/r04_k3f_diet.md)
+#endif
+#ifndef FA_F_SHLEV_MAXMLO
+#define FA_F_SHLEV_MAXMLO 12  // kernels with a larger maximum LPC order keep the per-wave solve
+#endif
+#ifndef FA_F_SHPOLL
+#define FA_F_SHPOLL 256  // polls of the ready flag before a wave solves its own problem after all (never an error, never a hang)
+#endif
+#ifndef FA_F_SHSLEEP
+#define FA_F_SHSLEEP 4  // x 64 cycles between two of those polls.  A sleeping wave costs the other waves of its SIMD nothing, a local solve
+                        // costs them 610 issue slots: the bound is generous, 256 x 256 cycles is most of a wave's life (a first bound
+                        // of 32 polls sent 4 % of the frames to the local solve)
+#endif
 #ifndef FA_F_PARKN
 #define FA_F_PARKN 32  // blocks that can wait in registers (an array of at most 32 registers is indexed in place, s_set_gpr_idx)
 #endif
@@ -313,12 +331,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
     __shared__ __attribute__((aligned(16))) int32_t lds_all[kFWaves * kFWaveWords];
     __shared__ __attribute__((aligned(16))) uint16_t crc_s[kFCrcSlice];
     __shared__ uint32_t ticket_s;
+    // hand-over of the workgroup's four LPC problems to one of its waves (see "LPC solve" below)
+    constexpr bool SHLEV = (FA_F_SHLEV != 0) && (MLO <= FA_F_SHLEV_MAXMLO);
+    static_assert(!SHLEV || kFRingWords >= 256 * kFWaves, "the solving wave works in its idle bit ring: 256 words per problem");
+    __shared__ double lev_in[SHLEV ? kFWaves : 1][MLO + 1];  // lag sums of frame w
+    __shared__ int lev_bps[SHLEV ? kFWaves : 1];             // its bits per sample, or -1: no LPC candidate
+    __shared__ int lev_out[SHLEV ? kFWaves : 1][MLO + 4];    // ok, order, precision, shift, coefficients
+    __shared__ uint32_t lev_rdy[SHLEV ? kFWaves : 1];        // lev_out[w] is complete
+    __shared__ uint32_t lev_cnt;                             // waves that have announced themselves
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int i = tid; i < kFCrcSlice / 2; i += 256) reinterpret_cast<uint32_t*>(crc_s)[i] = reinterpret_cast<const uint32_t*>(a.crc_tab)[i];
     if (tid == 0) ticket_s = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (SHLEV) {
+        if (tid == 0) lev_cnt = 0;
+        if (tid < kFWaves) lev_rdy[tid] = 0;
+    }
     __syncthreads();
     // (the ticket comes out of LDS, i.e. in a vector register: say that it is wave-uniform, so that the frame number, the
     // stream, the source pointer and everything else derived from it live in scalar registers)
@@ -328,17 +358,132 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
         return;
     }
     const int64_t g = (int64_t)(ticket - 1) * kFWaves + wave;
-    if (g >= a.total_frames) return;
 
     int32_t* smp = lds_all + wave * kFWaveWords;
     uint32_t* ring = reinterpret_cast<uint32_t*>(smp + kFSmpWords);
     uint8_t* kpar = reinterpret_cast<uint8_t*>(smp + kFSmpWords + kFRingWords + 4);
     uint32_t* scr = ring;  // analysis scratch before the ring is zeroed for the writer
+    constexpr int bs = kMaxBlock;
+
+    // ---- LPC solve: Levinson-Durbin, order choice, coefficient quantisation -------------------------------------------
+    // A serial computation on MLO + 1 numbers: ~610 vector instructions, a tenth of the kernel's stream, with one lane (or a
+    // handful) live.  lpc_solve runs it for `sub`-lane groups of GRP lanes: GRP = 64 is the per-wave form (one problem, the
+    // wave's own), GRP = 16 solves the workgroup's four problems side by side -- lane group w works on frame w, same
+    // instructions, same arithmetic.  wscr: 256 words of idle bit ring per problem.
+    auto lpc_solve = [&](auto grp_tag, const double (&ac)[MLO + 1], int fbps, uint32_t* wscr, int sub, int& wok, int& wlo, int& wprec,
+                         int& wsh, int32_t (&wq)[MLO]) __attribute__((always_inline)) {
+        constexpr int GRP = decltype(grp_tag)::value;
+        float* coef = reinterpret_cast<float*>(wscr);         // MLO*MLO floats
+        double* err = reinterpret_cast<double*>(wscr + 160);  // MLO doubles
+        int* meta = reinterpret_cast<int*>(wscr + 220);       // usable order
+        if (sub == 0) meta[0] = levinson<MLO>(ac, a.max_lpc_order, coef, err);
+        lds_fence();
+        const int usable = meta[0];
+        wprec = a.precision;
+        {
+            double mybits = 1e300;
+            if (sub < usable) {
+                const double e = err[sub];
+                const double error_scale = a.escale_full;
+                double bpsv;
+                if (e > 0.0) {
+                    bpsv = 0.5 * det_log2(error_scale * e);
+                    if (!(bpsv >= 0.0)) bpsv = 0.0;
+                } else if (e < 0.0) {
+                    bpsv = 1e32;
+                } else {
+                    bpsv = 0.0;
+                }
+                mybits = bpsv * (double)(bs - (sub + 1)) + (double)((sub + 1) * (fbps + wprec));
+            }
+            double bestb = 4294967295.0;
+            int bi = 0;
+            if constexpr (GRP == 64) {
+#pragma unroll
+                for (int o = 0; o < MLO; ++o) {
+                    const double b = readlane_f64(mybits, o);
+                    if (o < usable && b < bestb) { bestb = b; bi = o; }
+                }
+            } else {  // (the estimates of a group's orders through its scratch: a lane group cannot read lanes uniformly)
+                double* mbv = reinterpret_cast<double*>(wscr + 224);
+                if (sub < MLO) mbv[sub] = mybits;
+                lds_fence();
+#pragma unroll
+                for (int o = 0; o < MLO; ++o) {
+                    const double b = mbv[o];
+                    if (o < usable && b < bestb) { bestb = b; bi = o; }
+                }
+            }
+            wlo = bi + 1;
+        }
+        if (fbps <= 17) {
+            const int limp = 32 - fbps - ilog2_u64((uint64_t)wlo);
+            if (wprec > limp) wprec = limp;
+        }
+        wsh = 0;
+#pragma unroll
+        for (int j = 0; j < MLO; ++j) wq[j] = 0;
+        wok = 0;
+        if (wprec >= 2) wok = (quantize_coefs_t<MLO>(coef + (wlo - 1) * MLO, wlo, wprec, wq, &wsh) == 0) ? 1 : 0;
+    };
+    // The hand-over (FA_F_SHLEV).  Every wave of a frame workgroup ANNOUNCES itself exactly once, whatever its path: with
+    // its lag sums, or with "no LPC candidate" (a constant frame, all-zero lag sums, max_lpc_order 0, a wave without a
+    // frame).  The wave whose announcement completes the count is the SOLVING wave: everybody else's sums are in LDS by
+    // then (a wave's LDS operations execute in order), so it never waits; it writes lev_out, raises the four ready flags
+    // and goes on with its own frame.  The others run their FIXED analysis in the meantime and pick their result up
+    // afterwards (shlev_pickup); there is no barrier, and nobody depends on the solving wave: a wave that does not find
+    // its flag up within FA_F_SHPOLL polls solves its own problem the per-wave way.
+    auto shlev_announce = [&](bool cand, int fbps, const double* ac) __attribute__((always_inline)) {
+        const int ln = lane_id_opaque();
+        if (ln == 0) {
+            if (cand) {
+#pragma unroll
+                for (int j = 0; j <= MLO; ++j) lev_in[wave][j] = ac[j];
+            }
+            lev_bps[wave] = cand ? fbps : -1;
+        }
+        lds_fence();
+        uint32_t before = 0;
+        if (ln == 0) before = __hip_atomic_fetch_add(&lev_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        lds_fence();
+        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)before) != (uint32_t)(kFWaves - 1)) return;
+        // the solving wave
+        const int fr = ln >> 4, sub = ln & 15;
+        const int fbps_w = lev_bps[fr];
+        double acw[MLO + 1];
+#pragma unroll
+        for (int j = 0; j <= MLO; ++j) acw[j] = lev_in[fr][j];
+        if (fbps_w < 0) {  // (no candidate: whatever the slot holds is not looked at -- a harmless problem in its place)
+            acw[0] = 1.0;
+#pragma unroll
+            for (int j = 1; j <= MLO; ++j) acw[j] = 0.0;
+        }
+        int wok, wlo, wprec, wsh;
+        int32_t wq[MLO];
+        lpc_solve(std::integral_constant<int, 16>{}, acw, fbps_w, scr + 256 * fr, sub, wok, wlo, wprec, wsh, wq);
+        if (sub == 0) {
+            lev_out[fr][0] = wok; lev_out[fr][1] = wlo; lev_out[fr][2] = wprec; lev_out[fr][3] = wsh;
+#pragma unroll
+            for (int j = 0; j < MLO; ++j) lev_out[fr][4 + j] = wq[j];
+        }
+        lds_fence();
+        if (sub == 0) __hip_atomic_store(&lev_rdy[fr], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        lds_fence();
+    };
+    if constexpr (SHLEV) {
+        // a wave without a frame of its own (past the end, or a short last frame that the slot encoder wrote) announces before it leaves
+        bool mine = g < a.total_frames;
+        if (mine && a.tail_bs != kMaxBlock) mine = ((uint32_t)g % (uint32_t)a.nframes) != (uint32_t)(a.nframes - 1);
+        if (__builtin_expect(!mine, 0)) {
+            shlev_announce(false, 0, nullptr);
+            return;
+        }
+    }
+    if (g >= a.total_frames) return;
 
     const int64_t s = (int64_t)((uint32_t)g / (uint32_t)a.nframes);
     const int64_t f = g - s * a.nframes;
     if (f == a.nframes - 1 && a.tail_bs != kMaxBlock) return;  // a short last frame: encoded by the slot kernel
-    constexpr int bs = kMaxBlock;
     const int32_t* src = a.data + (s * a.stream_size + f * (int64_t)bs);
     float q_off = 0.0f, q_gain = 0.0f;
     if constexpr (F32IN) { q_off = a.f_offsets[s]; q_gain = a.f_gains[s]; }
@@ -455,11 +600,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
         return h;
     };
 
-    if (__builtin_expect(is_const, 0)) {
-        type = 0;
-    } else {
-        uint64_t best_bits = verbatim_bits;
-        // ---- P2: fixed predictors 0..4, lane partial sums over A_l then B_l -------------------------------
+    // Phase order.  FA_F_SHLEV: P0, P3 (lag products), announce, P2 (FIXED analysis, which does not depend on the LPC
+    // analysis and reads the same image: it fills the time of the shared solve), pick-up, P4.  Otherwise P0, P2, P3 with
+    // P2's partition search fused into the lag loops, per-wave solve, P4.  Either way the FIXED candidate is applied to
+    // best_bits first and the LPC candidate second, each with a strict <: the decisions are the same bit for bit.
+    uint64_t best_bits = verbatim_bits;
+    bool lpc_cand = false;  // the lag sums are in and not all zero: an LPC candidate follows
+    double autoc[MLO + 1];
+    // ---- P2: fixed predictors 0..4, lane partial sums over A_l then B_l; the FIXED candidate ----------------
+    uint64_t fixA = 0, fixB = 0, est_fix = 0;
+    int po_fix = 0, k_fix = 0, pmax_fix = 0;
+    bool fuse_search = false;  // the candidate's partition search runs in stages inside the lag loops (not FA_F_SHLEV)
+    auto apply_fixed = [&]() __attribute__((always_inline)) {
+        if (est_fix < best_bits) {
+            best_bits = est_fix;
+            type = 2;
+            order = fo;
+            porder = po_fix;
+            kbest = k_fix;
+        }
+    };
+    auto fixed_analysis = [&]() __attribute__((always_inline)) {
         double tot0 = 0.0, tot1 = 0.0, tot2 = 0.0, tot3 = 0.0, tot4 = 0.0;
         double mx0 = 0.0, mx1 = 0.0, mx2 = 0.0, mx3 = 0.0, mx4 = 0.0;
         // per-half sums of the winner are needed for the partition search: keep both halves of every order
@@ -587,7 +748,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
             if (M4 <= lim && T4 < smallest) { fo = 4; smallest = T4; }
         }
         // the winner's per-half magnitude sums (exact integers either way)
-        uint64_t fixA, fixB;
         if (narrow) {
             const uint64_t tA = (fo == 0) ? hA0 : (fo == 1) ? hA1 : (fo == 2) ? hA2 : (fo == 3) ? hA3 : hA4;
             const double tt = (fo == 0) ? tot0 : (fo == 1) ? tot1 : (fo == 2) ? tot2 : (fo == 3) ? tot3 : tot4;
@@ -599,22 +759,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
             fixA = (uint64_t)tA;
             fixB = (uint64_t)(tt - tA);
         }
-        int po_fix = 0, k_fix = 0;
-        const int pmax_fix = pmax_for(fo < 0 ? 0 : fo);
+        pmax_fix = pmax_for(fo < 0 ? 0 : fo);
         const bool small_fix = __all((fixA < (1u << 24)) && (fixB < (1u << 24)));
         win_small_f = small_fix;
-        const bool fuse_search = fo >= 0 && pmax_fix <= 5 && a.max_lpc_order > 0 && small_fix;
-        uint64_t est_fix = 0;
-        auto apply_fixed = [&]() __attribute__((always_inline)) {
-            if (est_fix < best_bits) {
-                best_bits = est_fix;
-                type = 2;
-                order = fo;
-                porder = po_fix;
-                kbest = k_fix;
-            }
-        };
-        if (__builtin_expect(fo >= 0 && !fuse_search, 0)) {
+        fuse_search = !SHLEV && fo >= 0 && pmax_fix <= 5 && a.max_lpc_order > 0 && small_fix;
+        if (__builtin_expect(fo >= 0 && !fuse_search, SHLEV ? 1 : 0)) {
             uint64_t rb;
             if (pmax_fix <= 5 && small_fix) {
                 SplitRiceSearch fs;
@@ -629,11 +778,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
             est_fix = 8 + (uint64_t)wasted + (uint64_t)fo * (uint64_t)bps + rb;
             apply_fixed();
         }
-
         FA_STAMP(2);
-        // ---- P3: LPC analysis ---------------------------------------------------------------------------
-        int mlo = a.max_lpc_order;
-        if (__builtin_expect(mlo > 0, 1)) {
+    };
+
+    if (__builtin_expect(is_const, 0)) {
+        type = 0;
+    } else {
+        if constexpr (!SHLEV) fixed_analysis();
+        // ---- P3: lag products and their wave sums -------------------------------------------------------
+        if (__builtin_expect(a.max_lpc_order > 0, 1)) {
             FA_IMAGE_ADDRS;
             double acc[MLO + 1];
 #pragma unroll
@@ -743,7 +896,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
                 est_fix = 8 + (uint64_t)wasted + (uint64_t)fo * (uint64_t)bps + (uint64_t)fs.best;
                 apply_fixed();
             }
-            double autoc[MLO + 1];
 #if FA_F_BFLY_N
 #pragma unroll
             for (int j = 0; j <= MLO; ++j) autoc[j] = acc[j];
@@ -752,198 +904,197 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
 #pragma unroll
             for (int j = 0; j <= MLO; ++j) autoc[j] = wave_sum_butterfly(acc[j]);
 #endif
+            lpc_cand = (autoc[0] != 0.0);
+        }
+    }
 
-            FA_STAMP(5);
-            if (__builtin_expect(autoc[0] != 0.0, 1)) {
-                float* coef = reinterpret_cast<float*>(scr);         // MLO*MLO floats
-                double* err = reinterpret_cast<double*>(scr + 160);  // MLO doubles
-                int* meta = reinterpret_cast<int*>(scr + 220);       // usable order
-                if (lane == 0) meta[0] = levinson<MLO>(autoc, mlo, coef, err);
-                lds_fence();
-                const int usable = meta[0];
-                int prec = a.precision;
-                int lo;
-                {
-                    double mybits = 1e300;
-                    if (lane < usable) {
-                        const double e = err[lane];
-                        const double error_scale = a.escale_full;
-                        double bpsv;
-                        if (e > 0.0) {
-                            bpsv = 0.5 * det_log2(error_scale * e);
-                            if (!(bpsv >= 0.0)) bpsv = 0.0;
-                        } else if (e < 0.0) {
-                            bpsv = 1e32;
-                        } else {
-                            bpsv = 0.0;
-                        }
-                        mybits = bpsv * (double)(bs - (lane + 1)) + (double)((lane + 1) * (bps + prec));
-                    }
-                    double bestb = 4294967295.0;
-                    int bi = 0;
+    FA_STAMP(5);
+    // ---- the LPC candidate's order, precision, shift and coefficients (see "LPC solve" above) ----------------
+    int ok = 0, lo = 0, prec = a.precision, sh = 0;
+    int32_t qreg[MLO];
 #pragma unroll
-                    for (int o = 0; o < MLO; ++o) {
-                        const double b = readlane_f64(mybits, o);
-                        if (o < usable && b < bestb) { bestb = b; bi = o; }
-                    }
-                    lo = bi + 1;
-                }
-                if (bps <= 17) {
-                    const int limp = 32 - bps - ilog2_u64((uint64_t)lo);
-                    if (prec > limp) prec = limp;
-                }
-                int sh = 0;
-                int32_t qreg[MLO];
-#pragma unroll
-                for (int j = 0; j < MLO; ++j) qreg[j] = 0;
-                int ok = 0;
-                if (prec >= 2) ok = (quantize_coefs_t<MLO>(coef + (lo - 1) * MLO, lo, prec, qreg, &sh) == 0) ? 1 : 0;
-                // (wave-uniform values read from LDS: say so, and they live in scalar registers from here to the preamble)
-                ok = __builtin_amdgcn_readfirstlane(ok);
-                sh = __builtin_amdgcn_readfirstlane(sh);
-#pragma unroll
-                for (int j = 0; j < MLO; ++j) qreg[j] = __builtin_amdgcn_readfirstlane(qreg[j]);
-                FA_STAMP(6);
-                if (__builtin_expect(ok != 0, 1)) {
-                    FA_IMAGE_ADDRS;
-                    const double scale = bitsd((uint64_t)(1023 - sh) << 52);  // 2^-sh (exact pre-scaling, see K3)
-                    double qd[MLO];
-#pragma unroll
-                    for (int j = 0; j < MLO; ++j) qd[j] = (double)qreg[j] * scale;
-                    // ---- P4: LPC residual in place (A in LDS, B in registers) + magnitude sums ----
-                    double tlA = 0.0, tlB = 0.0;
-                    double hx[MLO];
-                    // both histories are fetched before either half is overwritten
-                    const int4 a7 = *reinterpret_cast<const int4*>(&smp[hist7]), a6 = *reinterpret_cast<const int4*>(&smp[hist6]);
-                    const int4 a5 = *reinterpret_cast<const int4*>(&smp[hist5]);
-                    const int4 b7 = hist_b(Bv[7], *reinterpret_cast<const int4*>(&smp[tailA7]));
-                    const int4 b6 = hist_b(Bv[6], *reinterpret_cast<const int4*>(&smp[tailA6]));
-                    int4 b5 = make_int4(0, 0, 0, 0);
-                    if constexpr (MLO > 8) b5 = hist_b(Bv[5], *reinterpret_cast<const int4*>(&smp[tailA5]));
-                    lds_fence();
-                    // Per sample: MLO fma, floor, subtract, |r| into the lane sum, and the zig-zag fold taken in the double
-                    // domain -- trunc |2 r + 0.5| is 2 r for r >= 0 and -2 r - 1 for r < 0 (one fma and one conversion
-                    // instead of a conversion and three integer instructions).  A residual outside int32 (|r| >= 2^31,
-                    // which disqualifies the predictor) comes out as 0xffffffff, a value no valid residual folds to:
-                    // that is how the rare frame with such residuals is recognised below, without a per-sample maximum.
-                    auto fold_f64 = [&](double r) __attribute__((always_inline)) {
-                        return (int)(uint32_t)__builtin_fabs(__builtin_fma(r, 2.0, 0.5));
-                    };
-                    auto res_group = [&](auto mask_tag, const int4& xv, int gi0, double& tl) __attribute__((always_inline)) {
-                        constexpr bool MASK = decltype(mask_tag)::value;
-                        const int xs[4] = {xv.x, xv.y, xv.z, xv.w};
-                        int rs[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const double xd = (double)xs[e];
-#if FA_F_CEIL
-                            // r = x - floor(sum of q x / 2^sh) = ceil(x - sum): the sample seeds the chain (every partial sum is
-                            // an exact multiple of 2^-sh below 2^50, so the order of the terms is free)
-                            double t = xd;
-#pragma unroll
-                            for (int j = 0; j < MLO; ++j) t = __builtin_fma(-qd[j], hx[j], t);
-                            const double r = fa_ceil(t);
-#else
-                            double sum = 0.0;
-#pragma unroll
-                            for (int j = 0; j < MLO; ++j) sum = __builtin_fma(qd[j], hx[j], sum);
-                            const double pred = fa_floor(sum);
-                            const double r = xd - pred;
+    for (int j = 0; j < MLO; ++j) qreg[j] = 0;
+    if constexpr (SHLEV) {
+        shlev_announce(lpc_cand, bps, autoc);
+        FA_STAMP(6);
+        if (!is_const) fixed_analysis();
+        if (lpc_cand) {
+#ifdef FA_STAMPS
+            const unsigned long long tw0_ = fa_memtime();
 #endif
-                            if constexpr (MASK) {
-                                const bool v = (gi0 + e >= lo);
-                                tl += v ? fa_fabs(r) : 0.0;
-                                rs[e] = v ? fold_f64(r) : xs[e];
-                            } else {
-                                tl += fa_fabs(r);
-                                rs[e] = fold_f64(r);
-                            }
+            uint32_t up = 0, polls = 0;
+            for (;;) {
+                up = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&lev_rdy[wave], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                if (up != 0 || ++polls > (uint32_t)FA_F_SHPOLL) break;
+                __builtin_amdgcn_s_sleep(FA_F_SHSLEEP);
+            }
+            lds_fence();
+#ifdef FA_STAMPS
+            if (lane_id_opaque() == 0 && a.stamps && (blockIdx.x & 63) == 0) {  // cycles waited for the coefficients, polls, local solves, frames
+                atomicAdd(&a.stamps[17], fa_memtime() - tw0_);
+                atomicAdd(&a.stamps[18], (unsigned long long)polls);
+                atomicAdd(&a.stamps[19], up != 0 ? 0ULL : 1ULL);
+                atomicAdd(&a.stamps[20], 1ULL);
+            }
+#endif
+            if (__builtin_expect(up != 0, 1)) {
+                ok = lev_out[wave][0]; lo = lev_out[wave][1]; prec = lev_out[wave][2]; sh = lev_out[wave][3];
 #pragma unroll
-                            for (int j = MLO - 1; j > 0; --j) hx[j] = hx[j - 1];
-                            hx[0] = xd;
-                        }
-                        return make_int4(rs[0], rs[1], rs[2], rs[3]);
-                    };
-                    constexpr int kWarmGroups = (MLO + 3) / 4;
-                    {
-                        const int hs[12] = {a7.w, a7.z, a7.y, a7.x, a6.w, a6.z, a6.y, a6.x, a5.w, a5.z, a5.y, a5.x};
+                for (int j = 0; j < MLO; ++j) qreg[j] = lev_out[wave][4 + j];
+            } else {  // the solving wave is late (or left before it could know): this frame's problem the per-wave way
+                lpc_solve(std::integral_constant<int, 64>{}, autoc, bps, scr, lane_id_opaque(), ok, lo, prec, sh, qreg);
+            }
+        }
+    } else {
+        if (lpc_cand) lpc_solve(std::integral_constant<int, 64>{}, autoc, bps, scr, lane, ok, lo, prec, sh, qreg);
+        FA_STAMP(6);
+    }
+    // (wave-uniform values read from LDS: say so, and they live in scalar registers from here to the preamble)
+    ok = __builtin_amdgcn_readfirstlane(ok);
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    prec = __builtin_amdgcn_readfirstlane(prec);
+    sh = __builtin_amdgcn_readfirstlane(sh);
 #pragma unroll
-                        for (int j = 0; j < MLO; ++j) hx[j] = (double)hs[j];
+    for (int j = 0; j < MLO; ++j) qreg[j] = __builtin_amdgcn_readfirstlane(qreg[j]);
+    if (__builtin_expect(lpc_cand && ok != 0, 1)) {
+        FA_IMAGE_ADDRS;
+        const double scale = bitsd((uint64_t)(1023 - sh) << 52);  // 2^-sh (exact pre-scaling, see K3)
+        double qd[MLO];
 #pragma unroll
-                        for (int t = 0; t < 8; ++t) {
-                            int4* px = reinterpret_cast<int4*>(&smp[K ^ (4 * t)]);
-                            if (t < kWarmGroups) *px = res_group(std::true_type{}, *px, 32 * lane + 4 * t, tlA);
-                            else *px = res_group(std::false_type{}, *px, 0, tlA);
-                        }
-                    }
-                    {
-                        const int hs[12] = {b7.w, b7.z, b7.y, b7.x, b6.w, b6.z, b6.y, b6.x, b5.w, b5.z, b5.y, b5.x};
+        for (int j = 0; j < MLO; ++j) qd[j] = (double)qreg[j] * scale;
+        // ---- P4: LPC residual in place (A in LDS, B in registers) + magnitude sums ----
+        double tlA = 0.0, tlB = 0.0;
+        double hx[MLO];
+        // both histories are fetched before either half is overwritten
+        const int4 a7 = *reinterpret_cast<const int4*>(&smp[hist7]), a6 = *reinterpret_cast<const int4*>(&smp[hist6]);
+        const int4 a5 = *reinterpret_cast<const int4*>(&smp[hist5]);
+        const int4 b7 = hist_b(Bv[7], *reinterpret_cast<const int4*>(&smp[tailA7]));
+        const int4 b6 = hist_b(Bv[6], *reinterpret_cast<const int4*>(&smp[tailA6]));
+        int4 b5 = make_int4(0, 0, 0, 0);
+        if constexpr (MLO > 8) b5 = hist_b(Bv[5], *reinterpret_cast<const int4*>(&smp[tailA5]));
+        lds_fence();
+        // Per sample: MLO fma, floor, subtract, |r| into the lane sum, and the zig-zag fold taken in the double
+        // domain -- trunc |2 r + 0.5| is 2 r for r >= 0 and -2 r - 1 for r < 0 (one fma and one conversion
+        // instead of a conversion and three integer instructions).  A residual outside int32 (|r| >= 2^31,
+        // which disqualifies the predictor) comes out as 0xffffffff, a value no valid residual folds to:
+        // that is how the rare frame with such residuals is recognised below, without a per-sample maximum.
+        auto fold_f64 = [&](double r) __attribute__((always_inline)) {
+            return (int)(uint32_t)__builtin_fabs(__builtin_fma(r, 2.0, 0.5));
+        };
+        auto res_group = [&](auto mask_tag, const int4& xv, int gi0, double& tl) __attribute__((always_inline)) {
+            constexpr bool MASK = decltype(mask_tag)::value;
+            const int xs[4] = {xv.x, xv.y, xv.z, xv.w};
+            int rs[4];
 #pragma unroll
-                        for (int j = 0; j < MLO; ++j) hx[j] = (double)hs[j];
+            for (int e = 0; e < 4; ++e) {
+                const double xd = (double)xs[e];
+#if FA_F_CEIL
+                // r = x - floor(sum of q x / 2^sh) = ceil(x - sum): the sample seeds the chain (every partial sum is
+                // an exact multiple of 2^-sh below 2^50, so the order of the terms is free)
+                double t = xd;
 #pragma unroll
-                        for (int t = 0; t < 8; ++t) Bv[t] = res_group(std::false_type{}, Bv[t], 0, tlB);
-                    }
-                    FA_STAMP(7);
-                    img_is_residual = true;
-                    const int pmax = pmax_for(lo);
-                    int po_l = 0, k_l = 0;
-                    uint64_t rbits;
-                    const bool small_l = __all((tlA < 16777216.0) && (tlB < 16777216.0));
-                    // every |r| is below its lane's sum: with small sums no residual leaves int32.  Otherwise (wide samples)
-                    // look for the mark of an out-of-range residual among the folded values (warm-up samples are not residuals)
-                    bool lpc_in_range = true;
-                    if (__builtin_expect(!small_l, 0)) {
-                        bool hit = false;
-#pragma unroll 1
-                        for (int t = 0; t < 8; ++t) {
-                            const int4 ra = *reinterpret_cast<const int4*>(&smp[K ^ (4 * t)]);
-                            const int ras[4] = {ra.x, ra.y, ra.z, ra.w};
+                for (int j = 0; j < MLO; ++j) t = __builtin_fma(-qd[j], hx[j], t);
+                const double r = fa_ceil(t);
+#else
+                double sum = 0.0;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) hit = hit || ((32 * lane + 4 * t + e >= lo) && (uint32_t)ras[e] == 0xffffffffu);
-                        }
-#pragma unroll
-                        for (int t = 0; t < 8; ++t)
-                            hit = hit || (uint32_t)Bv[t].x == 0xffffffffu || (uint32_t)Bv[t].y == 0xffffffffu || (uint32_t)Bv[t].z == 0xffffffffu ||
-                                  (uint32_t)Bv[t].w == 0xffffffffu;
-                        lpc_in_range = !__any(hit);
-                    }
-                    win_small_l = small_l;
-                    if (pmax <= 5 && small_l) {
-                        SplitRiceSearch ls;
-                        ls.start((uint32_t)tlA, (uint32_t)tlB, lo, pmax, lane);
-                        ls.gather(); ls.params(); ls.totals();
-#pragma unroll
-                        for (int o = 5; o >= 0; --o) ls.order(o);
-                        po_l = ls.bpo; k_l = ls.kb; rbits = ls.best;
-                    } else {
-                        rbits = split_rice_search_slow((uint64_t)tlA, (uint64_t)tlB, lo, pmax, lane, &po_l, &k_l);
-                    }
-                    if (lpc_in_range) {
-                        const uint64_t est = 8 + (uint64_t)wasted + 4 + 5 + (uint64_t)lo * (uint64_t)(prec + bps) + rbits;
-                        if (est < best_bits) {
-                            best_bits = est;
-                            type = 3;
-                            order = lo;
-                            porder = po_l;
-                            kbest = k_l;
-                            shift = sh;
-                            precision = prec;
-#pragma unroll
-                            for (int j = 0; j < MLO; ++j) qkeep[j] = qreg[j];
-                        }
-                    }
+                for (int j = 0; j < MLO; ++j) sum = __builtin_fma(qd[j], hx[j], sum);
+                const double pred = fa_floor(sum);
+                const double r = xd - pred;
+#endif
+                if constexpr (MASK) {
+                    const bool v = (gi0 + e >= lo);
+                    tl += v ? fa_fabs(r) : 0.0;
+                    rs[e] = v ? fold_f64(r) : xs[e];
+                } else {
+                    tl += fa_fabs(r);
+                    rs[e] = fold_f64(r);
                 }
-                lds_fence();
+#pragma unroll
+                for (int j = MLO - 1; j > 0; --j) hx[j] = hx[j - 1];
+                hx[0] = xd;
+            }
+            return make_int4(rs[0], rs[1], rs[2], rs[3]);
+        };
+        constexpr int kWarmGroups = (MLO + 3) / 4;
+        {
+            const int hs[12] = {a7.w, a7.z, a7.y, a7.x, a6.w, a6.z, a6.y, a6.x, a5.w, a5.z, a5.y, a5.x};
+#pragma unroll
+            for (int j = 0; j < MLO; ++j) hx[j] = (double)hs[j];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                int4* px = reinterpret_cast<int4*>(&smp[K ^ (4 * t)]);
+                if (t < kWarmGroups) *px = res_group(std::true_type{}, *px, 32 * lane + 4 * t, tlA);
+                else *px = res_group(std::false_type{}, *px, 0, tlA);
+            }
+        }
+        {
+            const int hs[12] = {b7.w, b7.z, b7.y, b7.x, b6.w, b6.z, b6.y, b6.x, b5.w, b5.z, b5.y, b5.x};
+#pragma unroll
+            for (int j = 0; j < MLO; ++j) hx[j] = (double)hs[j];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) Bv[t] = res_group(std::false_type{}, Bv[t], 0, tlB);
+        }
+        FA_STAMP(7);
+        img_is_residual = true;
+        const int pmax = pmax_for(lo);
+        int po_l = 0, k_l = 0;
+        uint64_t rbits;
+        const bool small_l = __all((tlA < 16777216.0) && (tlB < 16777216.0));
+        // every |r| is below its lane's sum: with small sums no residual leaves int32.  Otherwise (wide samples)
+        // look for the mark of an out-of-range residual among the folded values (warm-up samples are not residuals)
+        bool lpc_in_range = true;
+        if (__builtin_expect(!small_l, 0)) {
+            bool hit = false;
+#pragma unroll 1
+            for (int t = 0; t < 8; ++t) {
+                const int4 ra = *reinterpret_cast<const int4*>(&smp[K ^ (4 * t)]);
+                const int ras[4] = {ra.x, ra.y, ra.z, ra.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) hit = hit || ((32 * lane + 4 * t + e >= lo) && (uint32_t)ras[e] == 0xffffffffu);
+            }
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                hit = hit || (uint32_t)Bv[t].x == 0xffffffffu || (uint32_t)Bv[t].y == 0xffffffffu || (uint32_t)Bv[t].z == 0xffffffffu ||
+                      (uint32_t)Bv[t].w == 0xffffffffu;
+            lpc_in_range = !__any(hit);
+        }
+        win_small_l = small_l;
+        if (pmax <= 5 && small_l) {
+            SplitRiceSearch ls;
+            ls.start((uint32_t)tlA, (uint32_t)tlB, lo, pmax, lane);
+            ls.gather(); ls.params(); ls.totals();
+#pragma unroll
+            for (int o = 5; o >= 0; --o) ls.order(o);
+            po_l = ls.bpo; k_l = ls.kb; rbits = ls.best;
+        } else {
+            rbits = split_rice_search_slow((uint64_t)tlA, (uint64_t)tlB, lo, pmax, lane, &po_l, &k_l);
+        }
+        if (lpc_in_range) {
+            const uint64_t est = 8 + (uint64_t)wasted + 4 + 5 + (uint64_t)lo * (uint64_t)(prec + bps) + rbits;
+            if (est < best_bits) {
+                best_bits = est;
+                type = 3;
+                order = lo;
+                porder = po_l;
+                kbest = k_l;
+                shift = sh;
+                precision = prec;
+#pragma unroll
+                for (int j = 0; j < MLO; ++j) qkeep[j] = qreg[j];
             }
         }
     }
+    lds_fence();
 
     FA_STAMP(8);
     // (the lane number of the writer half of the kernel is a fresh copy: the one taken at the top would otherwise stay
     // alive across the register peak of the lag loops, and the compiler keeps it in scratch memory there)
     const int lane_w = lane_id_opaque();
     // ---- materialise the winner's residual: LPC is in place; FIXED is recomputed from the samples -------
-    auto reload_image = [&]() __attribute__((always_inline)) {
+    // (FOLD: the image is wanted zig-zag folded -- the residual of FIXED order 0 is the sample itself)
+    auto reload_image = [&](auto fold_tag) __attribute__((always_inline)) {
+        constexpr bool FOLD = decltype(fold_tag)::value;
         FA_IMAGE_ADDRS;
 #pragma unroll 1
         for (int half = 1; half >= 0; --half) {
@@ -951,6 +1102,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
             for (int j = 0; j < 8; ++j) {
                 int4 v = load_row(8 * half + j);
                 v.x >>= wasted; v.y >>= wasted; v.z >>= wasted; v.w >>= wasted;
+                if constexpr (FOLD) { v.x = rice_fold(v.x); v.y = rice_fold(v.y); v.z = rice_fold(v.z); v.w = rice_fold(v.w); }
                 *reinterpret_cast<int4*>(&smp[rowbase + 256 * j]) = v;
             }
             if (half == 1) {
@@ -960,12 +1112,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
         }
         lds_fence();
     };
-    if (__builtin_expect(type == 2, 0)) {
+    if (__builtin_expect(type == 2 && order == 0, 0)) {
+        // FIXED order 0 (a twelfth of the headline workload's frames: noise that no predictor helps): the residual is the
+        // sample, so the frame needs only the fold, in 32 bits and on the way into the image -- no second pass, no 64-bit
+        // predictor arithmetic.  These frames publish their size last of all kinds (they have been through the LPC
+        // candidate as well), and every frame behind them waits for it.
         if (img_is_residual) {
-            reload_image();
+            reload_image(std::true_type{});
+        } else {
+            FA_IMAGE_ADDRS;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                int4* px = reinterpret_cast<int4*>(&smp[K ^ (4 * t)]);
+                int4 v = *px;
+                v.x = rice_fold(v.x); v.y = rice_fold(v.y); v.z = rice_fold(v.z); v.w = rice_fold(v.w);
+                *px = v;
+                Bv[t].x = rice_fold(Bv[t].x); Bv[t].y = rice_fold(Bv[t].y); Bv[t].z = rice_fold(Bv[t].z); Bv[t].w = rice_fold(Bv[t].w);
+            }
+            lds_fence();
+        }
+        img_is_residual = true;
+    } else if (__builtin_expect(type == 2, 0)) {
+        if (img_is_residual) {
+            reload_image(std::false_type{});
             img_is_residual = false;
         }
-        {   // (order 0: the residual is the sample itself, folded like any other)
+        {   // (orders 1..4)
             FA_IMAGE_ADDRS;
             const int4 ha = *reinterpret_cast<const int4*>(&smp[hist7]);
             const int4 hb2 = hist_b(Bv[7], *reinterpret_cast<const int4*>(&smp[tailA7]));
@@ -1077,8 +1249,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
 #ifdef FA_TIMELINE
     // diagnostic build: the optional FrameInfo record carries 100 MHz timestamps instead of the decisions
     // (wasted = start, shift = size published, porder = offset out (written by the scanner), precision = offset asked
-    // for, blocksize = offset seen)
+    // for, blocksize = offset seen; type and order are the decisions, so that the times can be split by kind of frame)
     if (lane_w == 0 && a.info) {
+        a.info[g].type = type;
+        a.info[g].order = (type >= 2) ? order : 0;
         a.info[g].wasted = (int32_t)tl_start_;
         a.info[g].shift = (int32_t)(uint32_t)__builtin_amdgcn_s_memrealtime();
         __builtin_amdgcn_s_waitcnt(0);

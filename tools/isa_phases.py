@@ -25,7 +25,7 @@ PHASES = {
     "1": "P2 wave sums, order choice, (unfused) partition search",
     "2": "P3 lag products (9 f64 chains per sample) + fused fixed partition search",
     "4": "P3 nine wave sums (butterfly)",
-    "5": "Levinson-Durbin, order choice, coefficient quantisation",
+    "5": "LPC solve: Levinson-Durbin, order choice, coefficient quantisation",
     "6": "P4 LPC residual in place + magnitude sums",
     "7": "LPC partition search, winner bookkeeping",
     "8": "materialise the winner (FIXED recompute), exact size of the winner",
@@ -35,6 +35,17 @@ PHASES = {
     "13": "tail: CRC-16 of the remaining words, last stores",
     "12": "(end)",
 }
+
+
+# the shipped phase order (FA_F_SHLEV=1): the lag products follow P0, the FIXED analysis fills the time of the shared solve
+PHASES_SHLEV = dict(PHASES)
+PHASES_SHLEV.update({
+    "0": "P3 lag products (9 f64 chains per sample)",
+    "5": "announce; the solving wave only: the workgroup's four LPC problems side by side (Levinson-Durbin, order choice, quantisation)",
+    "6": "P2 fixed predictors 0-4 (lane sums over A then B)",
+    "1": "P2 wave sums, order choice, partition search",
+    "2": "pick-up of order / precision / shift / coefficients (poll, local solve as the fallback), P4 LPC residual in place + magnitude sums",
+})
 
 
 def classify(op):
@@ -115,6 +126,7 @@ def main():
                 cur["loops"].append((lab, n))
     ranges.append((cur_name, cur))
     trips = dict(kv.split("=") for kv in args.trips.split(",") if kv)
+    phases = PHASES if "-DFA_F_SHLEV=0" in defines else PHASES_SHLEV
     print(f"kernel `{args.kernel}` {' '.join(defines)}: " + ", ".join(f"{k} {v}" for k, v in meta.items()))
     print()
     print("| after mark | phase | VALU | of which 64-bit | DPP | SALU | LDS | global | scratch | waits | loops (label: VALU in body) |")
@@ -126,7 +138,7 @@ def main():
         for k in ("valu", "f64", "dpp", "salu", "lds", "vmem", "scratch", "wait"):
             tot[k] += c[k]
         loops = "; ".join(f"{lab}: {n}" for lab, n in c["loops"])
-        print(f"| {name} | {PHASES.get(name, name)} | {c['valu']} | {c['f64']} | {c['dpp']} | {c['salu']} | {c['lds']} | {c['vmem']} | {c['scratch']} | {c['wait']} | {loops} |")
+        print(f"| {name} | {phases.get(name, name)} | {c['valu']} | {c['f64']} | {c['dpp']} | {c['salu']} | {c['lds']} | {c['vmem']} | {c['scratch']} | {c['wait']} | {loops} |")
     print(f"| | **layout total (loop bodies once)** | {tot['valu']} | {tot['f64']} | {tot['dpp']} | {tot['salu']} | {tot['lds']} | {tot['vmem']} | {tot['scratch']} | {tot['wait']} | |")
     print(f"| | cold blocks behind s_endpgm | {cold['valu']} | {cold['f64']} | {cold['dpp']} | {cold['salu']} | {cold['lds']} | {cold['vmem']} | {cold['scratch']} | {cold['wait']} | |")
     if args.keep:

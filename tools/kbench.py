@@ -65,6 +65,9 @@ def main():
             n_ = max(buf[32 + 4 * x], 1)
             print(f"  XCD {x}: frames {buf[32 + 4 * x]:6d}  offset wait {buf[33 + 4 * x] / n_:8.0f}  lifetime {buf[34 + 4 * x] / n_:8.0f}  start->publish {buf[35 + 4 * x] / n_:8.0f}")
         print(f"  (of rows: flush calls   {buf[15]/max(tot,1)*100:6.2f} %   {buf[15]/nfr:10.0f} cyc/frame)")
+        if buf[20]:  # the shared LPC solve (FA_F_SHLEV): the sampled frames that had an LPC candidate
+            print(f"  shared LPC solve: {buf[20]} frames picked up, waited {buf[17]/buf[20]:.0f} cyc/frame for the coefficients, "
+                  f"{buf[18]/buf[20]:.3f} polls/frame, {buf[19]} solved locally after all")
     if args.check:
         from oracle import oracle as O
 

@@ -37,6 +37,15 @@ def main():
     show("own publish -> all predecessors published (stragglers)", front - pub)
     show("all predecessors published -> offset stored (scanner)", off - front)
     show("offset stored -> seen by the frame (poll), where it waited", np.where(off > req, got - off, 0))
+    # by kind of frame (type 0 constant, 1 VERBATIM, 2 FIXED, 3 LPC): a kind that publishes late holds up everyone behind it
+    ftype, forder = info.cpu().numpy()[:, 0], info.cpu().numpy()[:, 1]
+    for ty in range(4):
+        m = ftype[lo:hi] == ty
+        if m.any():
+            v = (pub - start)[lo:hi][m] * tick / 1000.0
+            ords = np.bincount(forder[lo:hi][m], minlength=1)
+            print(f"  type {ty}: {int(m.sum()):7d} frames ({100.0 * m.mean():5.1f} %), start -> size published mean {v.mean():8.2f} us   median {np.median(v):8.2f}"
+                  f"   p90 {np.percentile(v, 90):8.2f}   orders {dict((int(o), int(c)) for o, c in enumerate(ords) if c)}")
     order = np.argsort(start, kind="stable")
     print("  frames whose start order differs from ticket order:", int((np.diff(start) < 0).sum()))
 
