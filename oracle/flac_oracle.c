@@ -196,6 +196,49 @@ static int ilog2_u64(uint64_t v) { /* floor(log2(v)), v > 0 */
 }
 
 /* ------------------------------------------------------------------------------------------
+ * Decision trace (oracle_encode_stream_trace*): one record per subframe with the CAUSE of every decision, for the
+ * encoder corpus audit (tests/encoder_corpus.py).  The encoder reports through the thread-local pointers below, which
+ * are NULL on every other path: nothing the oracle computes or writes depends on them.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    /* the fields of oracle_frame_info, same meaning */
+    int32_t type, order, porder, wasted, shift, precision, nbytes, blocksize;
+    int32_t bps;          /* bits per sample after the wasted bits (33 - wasted for a side subframe) */
+    int32_t is_const;
+    int32_t fixed_valid;  /* bit k: FIXED order k has no residual beyond INT32_MAX (0 when FIXED was not searched) */
+    int32_t fixed_order;  /* the FIXED order with the smallest total, -1: none valid / not searched */
+    int32_t lpc_tried;    /* the level has LPC and the frame more than 4 samples */
+    int32_t lpc_drop;     /* TR_LPC_*: 0 = LPC is the candidate, else why not */
+    int32_t quant_rc;     /* quantize_coefs return code, -1 when it was not called */
+    int32_t lev_usable;   /* the order levinson() called usable */
+    int32_t lev_neg, lev_zero; /* an error of Levinson's recursion was < 0 / == 0 */
+    int32_t lpc_order;    /* best_lpc_order's choice */
+    int32_t prec_before, prec_after; /* coefficient precision before / after the bps <= 17 limit */
+    int32_t raw_shift;    /* quantize_coefs: the shift before its clamp at 15 */
+    int32_t clamp_qmax, clamp_qmin;  /* a coefficient was clamped there */
+    int32_t cand_type;    /* type before the exact-size / row-cap fall-back to VERBATIM */
+    int32_t rice_min, rice_max, rice2; /* of the candidate's residual (cand_type >= 2) */
+    int32_t rice_clamp30; /* a Rice search of this subframe (FIXED or LPC, any partition order) clamped a parameter at 30 */
+    int32_t row_over, exact_over;    /* the fall-back tests */
+    int32_t verbatim_cause;          /* TR_VERB_*: 0 = not VERBATIM */
+    int32_t channel, nch;
+    int32_t st_fits, st_small, st_right_zero, st_tried, st_use_side; /* two-channel frames (both subframes carry them) */
+    int32_t st_fit_sign;  /* !st_fits: +1 the first side value out of range is above INT32_MAX, -1 below INT32_MIN */
+    int64_t st_est_left, st_est_side; /* valid when st_tried */
+    int64_t est_bits;     /* estimate of the candidate */
+    int64_t exact_bits;   /* exact size of the candidate (cand_type >= 2) */
+    int64_t verbatim_bits;
+    double cmax;          /* quantize_coefs: the largest coefficient magnitude */
+} oracle_trace_rec;
+
+enum { TR_LPC_WON = 0, TR_LPC_NOT_TRIED, TR_LPC_LAGS_ZERO, TR_LPC_CMAX, TR_LPC_QUANT_RC, TR_LPC_PREC, TR_LPC_RESIDUAL,
+       TR_LPC_RICE, TR_LPC_ESTIMATE };
+enum { TR_VERB_NONE = 0, TR_VERB_SHORT, TR_VERB_NO_CANDIDATE, TR_VERB_ROW_CAP, TR_VERB_EXACT };
+
+static __thread oracle_trace_rec *g_trace = NULL; /* the stream's records, [frame * nch + channel] */
+static __thread oracle_trace_rec *g_tcur = NULL;  /* the subframe being written (NULL in analysis-only passes) */
+
+/* ------------------------------------------------------------------------------------------
  * Partitioned-Rice parameter search on integer partition sums
  * (after libFLAC find_best_partition_order_/set_partitioned_rice_/count_rice_bits_in_partition_)
  * ---------------------------------------------------------------------------------------- */
@@ -248,7 +291,7 @@ static bool rice_search(const int32_t *res, int bs, int pred_order, int level_ma
             int k;
             if (mean < 2 || (((mean - 1) * fpd) >> 18) == 0) k = 0;
             else k = ilog2_u64(((mean - 1) * fpd) >> 18) + 1;
-            if (k >= RICE_LIMIT) k = RICE_LIMIT - 1;
+            if (k >= RICE_LIMIT) { k = RICE_LIMIT - 1; if (g_tcur) g_tcur->rice_clamp30 = 1; }
             uint64_t pb = 4 + (uint64_t)(1 + k) * (uint64_t)n + (k ? (mean >> (k - 1)) : (mean << 1)) - (uint64_t)(n >> 1);
             if (pb > 0xffffffffULL) pb = 0xffffffffULL;
             bits += pb;
@@ -360,6 +403,10 @@ static int levinson(const double *autoc, int max_order, float coef[][MAX_ORDER],
         err = err * (1.0 - r * r);
         for (j = 0; j <= i; ++j) coef[i][j] = (float)(-lpc[j]);
         err_out[i] = err;
+        if (g_tcur) {
+            if (err < 0.0) g_tcur->lev_neg = 1;
+            if (err == 0.0) g_tcur->lev_zero = 1;
+        }
         if (err == 0.0) return i + 1;
     }
     return max_order;
@@ -395,12 +442,14 @@ static int quantize_coefs(const float *c, int order, int precision, int32_t *q, 
         double d = fabs((double)c[i]);
         if (d > cmax) cmax = d;
     }
+    if (g_tcur) g_tcur->cmax = cmax;
     if (cmax <= 0.0) return 2;
     /* log2cmax = floor(log2(cmax)) from the exponent field (cmax is a normal float value) */
     uint64_t b;
     memcpy(&b, &cmax, 8);
     int log2cmax = (int)((b >> 52) & 0x7ff) - 1023;
     int sh = precision - log2cmax - 1;
+    if (g_tcur) g_tcur->raw_shift = sh;
     if (sh > 15) sh = 15;
     else if (sh < -16) return 1;
     double error = 0.0;
@@ -408,8 +457,8 @@ static int quantize_coefs(const float *c, int order, int precision, int32_t *q, 
         for (int i = 0; i < order; ++i) {
             error = error + (double)c[i] * (double)(1 << sh);
             double rq = (error >= 0.0) ? floor(error + 0.5) : ceil(error - 0.5);
-            if (rq > (double)qmax) rq = (double)qmax;
-            else if (rq < (double)qmin) rq = (double)qmin;
+            if (rq > (double)qmax) { rq = (double)qmax; if (g_tcur) g_tcur->clamp_qmax = 1; }
+            else if (rq < (double)qmin) { rq = (double)qmin; if (g_tcur) g_tcur->clamp_qmin = 1; }
             error = error - rq;
             q[i] = (int32_t)rq;
         }
@@ -419,8 +468,8 @@ static int quantize_coefs(const float *c, int order, int precision, int32_t *q, 
         for (int i = 0; i < order; ++i) {
             error = error + (double)c[i] / (double)(1 << nshift);
             double rq = (error >= 0.0) ? floor(error + 0.5) : ceil(error - 0.5);
-            if (rq > (double)qmax) rq = (double)qmax;
-            else if (rq < (double)qmin) rq = (double)qmin;
+            if (rq > (double)qmax) { rq = (double)qmax; if (g_tcur) g_tcur->clamp_qmax = 1; }
+            else if (rq < (double)qmin) { rq = (double)qmin; if (g_tcur) g_tcur->clamp_qmin = 1; }
             error = error - rq;
             q[i] = (int32_t)rq;
         }
@@ -479,6 +528,9 @@ static uint64_t encode_subframe(bitw_t *w, const int32_t *xin_s, int stride, int
                                 oracle_frame_info *info, int bps_base) {
     static __thread int32_t xin[MAX_BLOCK], x[MAX_BLOCK], rfix[MAX_BLOCK], rlpc[MAX_BLOCK];
     for (int i = 0; i < bs; ++i) xin[i] = xin_s[(size_t)i * (size_t)stride];
+    oracle_trace_rec *T = w ? g_tcur : NULL; /* (encode_frame points g_tcur at this subframe's record) */
+    g_tcur = T;
+    if (T) { T->fixed_order = -1; T->quant_rc = -1; T->lpc_drop = TR_LPC_NOT_TRIED; }
 
     /* ---- wasted bits ---- */
     uint32_t orv = 0;
@@ -525,6 +577,10 @@ static uint64_t encode_subframe(bitw_t *w, const int32_t *xin_s, int stride, int
         uint64_t smallest = UINT64_MAX;
         for (int k = 0; k < 5; ++k)
             if (valid[k] && tot[k] < smallest) { fo = k; smallest = tot[k]; }
+        if (T) {
+            for (int k = 0; k < 5; ++k) T->fixed_valid |= valid[k] ? (1 << k) : 0;
+            T->fixed_order = fo;
+        }
         if (fo >= 0) {
             for (int i = 0; i < bs; ++i) {
                 int64_t e;
@@ -550,17 +606,21 @@ static uint64_t encode_subframe(bitw_t *w, const int32_t *xin_s, int stride, int
             double autoc[MAX_ORDER + 1], err[MAX_ORDER];
             static __thread float coef[MAX_ORDER][MAX_ORDER];
             autocorr_lanes(x, win, bs, mlo + 1, autoc);
+            if (T) { T->lpc_tried = 1; T->lpc_drop = TR_LPC_LAGS_ZERO; }
             if (autoc[0] != 0.0) {
                 int usable = levinson(autoc, mlo, coef, err);
                 int prec = P->qlp_precision;
                 int lo = best_lpc_order(err, usable, bs, bps + prec);
+                if (T) { T->lev_usable = usable; T->lpc_order = lo; T->prec_before = prec; }
                 if (bps <= 17) {
                     int lim = 32 - bps - ilog2_u64((uint64_t)lo);
                     if (prec > lim) prec = lim;
                 }
                 int32_t q[MAX_ORDER];
                 int sh;
-                if (prec >= 2 && quantize_coefs(coef[lo - 1], lo, prec, q, &sh) == 0) {
+                int qrc = -1;
+                if (T) { T->prec_after = prec; T->lpc_drop = TR_LPC_PREC; }
+                if (prec >= 2 && (qrc = quantize_coefs(coef[lo - 1], lo, prec, q, &sh)) == 0) {
                     bool ok = true;
                     for (int i = 0; i < bs; ++i) {
                         if (i < lo) { rlpc[i] = x[i]; continue; }
@@ -570,25 +630,56 @@ static uint64_t encode_subframe(bitw_t *w, const int32_t *xin_s, int stride, int
                         if (r > 2147483647LL || r < -2147483647LL) { ok = false; break; }
                         rlpc[i] = (int32_t)r;
                     }
+                    if (T) T->lpc_drop = ok ? TR_LPC_RICE : TR_LPC_RESIDUAL;
                     if (ok && rice_search(rlpc, bs, lo, P->max_porder, &rc_lpc)) {
                         uint64_t est = 8 + (uint64_t)wasted + 4 + 5 + (uint64_t)lo * (uint64_t)(prec + bps) + rc_lpc.est_bits;
+                        if (T) T->lpc_drop = TR_LPC_ESTIMATE;
                         if (est < best_bits) {
+                            if (T) T->lpc_drop = TR_LPC_WON;
                             best_bits = est; type = 3; order = lo; rc = rc_lpc; res = rlpc;
                             shift = sh; precision = prec;
                             memcpy(qcoef, q, sizeof(int32_t) * (size_t)lo);
                         }
                     }
+                } else if (T && prec >= 2) {
+                    T->lpc_drop = (qrc == 2) ? TR_LPC_CMAX : TR_LPC_QUANT_RC;
                 }
+                if (T) T->quant_rc = qrc;
             }
         }
         /* exact size of the winner; fall back to VERBATIM when it is larger or a row is too long */
+        if (T) T->cand_type = type;
         if (type >= 2) {
             bool rowov;
             uint64_t exact = 8 + (uint64_t)wasted + (uint64_t)order * (uint64_t)bps + rice_exact_bits(res, bs, order, &rc, &rowov);
             if (type == 3) exact += 4 + 5 + (uint64_t)order * (uint64_t)precision;
+            if (T) {
+                T->rice_min = 31; T->rice_max = 0;
+                for (int p = 0; p < (1 << rc.porder); ++p) {
+                    if (rc.params[p] < T->rice_min) T->rice_min = rc.params[p];
+                    if (rc.params[p] > T->rice_max) T->rice_max = rc.params[p];
+                }
+                T->rice2 = T->rice_max >= 15;
+                T->row_over = rowov; T->exact_over = exact > verbatim_bits; T->exact_bits = (int64_t)exact;
+                T->verbatim_cause = rowov ? TR_VERB_ROW_CAP : (exact > verbatim_bits ? TR_VERB_EXACT : TR_VERB_NONE);
+            }
             if (rowov || exact > verbatim_bits) type = 1;
+        } else if (T) {
+            T->verbatim_cause = TR_VERB_NO_CANDIDATE;
         }
+    } else if (T) {
+        T->cand_type = 1;
+        T->verbatim_cause = TR_VERB_SHORT;
     }
+    if (T) {
+        T->is_const = is_const; T->bps = bps; T->est_bits = (int64_t)best_bits; T->verbatim_bits = (int64_t)verbatim_bits;
+        T->type = type; T->wasted = wasted; T->blocksize = bs;
+        T->order = (type >= 2) ? order : 0;
+        T->porder = (type >= 2) ? rc.porder : 0;
+        T->shift = (type == 3) ? shift : 0;
+        T->precision = (type == 3) ? precision : 0;
+    }
+    g_tcur = NULL;
 
     if (!w) return best_bits;
 
@@ -645,20 +736,34 @@ static void encode_frame(bitw_t *w, const int32_t *xin, int nch, int bs, uint64_
     size_t frame_start = (size_t)(w->nbits >> 3);
     static __thread int32_t side[MAX_BLOCK];
     bool use_side = false;
+    oracle_trace_rec *TR = g_trace ? &g_trace[frame_no * (uint64_t)nch] : NULL;
+    g_tcur = NULL;
+    if (TR)
+        for (int c = 0; c < nch; ++c) { TR[c].channel = c; TR[c].nch = nch; }
     if (nch == 2) {
         bool fits = true, right_zero = true, small = true;
         for (int i = 0; i < bs; ++i) {
             const int64_t d = (int64_t)xin[2 * i] - (int64_t)xin[2 * i + 1];
             if (xin[2 * i + 1] != 0) right_zero = false;
             if (xin[2 * i] >= STEREO_SMALL || xin[2 * i] <= -STEREO_SMALL) small = false;
-            if (d > 2147483647LL || d < -2147483648LL) { fits = false; break; }
+            if (d > 2147483647LL || d < -2147483648LL) {
+                fits = false;
+                if (TR) TR[0].st_fit_sign = TR[1].st_fit_sign = d > 0 ? 1 : -1;
+                break;
+            }
             side[i] = (int32_t)d;
         }
         if (fits && small && !right_zero) {
             const uint64_t est_left = encode_subframe(NULL, xin, 2, bs, P, win, NULL, 32);
             const uint64_t est_side = encode_subframe(NULL, side, 1, bs, P, win, NULL, 33);
             use_side = est_side < est_left;
+            if (TR)
+                for (int c = 0; c < 2; ++c) { TR[c].st_tried = 1; TR[c].st_est_left = (int64_t)est_left; TR[c].st_est_side = (int64_t)est_side; }
         }
+        if (TR)
+            for (int c = 0; c < 2; ++c) {
+                TR[c].st_fits = fits; TR[c].st_small = small; TR[c].st_right_zero = right_zero; TR[c].st_use_side = use_side;
+            }
     }
 
     /* ---- frame header (RFC 9639 9.1) ---- */
@@ -675,6 +780,7 @@ static void encode_frame(bitw_t *w, const int32_t *xin, int nch, int bs, uint64_
     bw_put(w, crc8(w->buf + frame_start, (size_t)(w->nbits >> 3) - frame_start), 8);
 
     for (int c = 0; c < nch; ++c) {
+        g_tcur = TR ? &TR[c] : NULL;
         if (c == 0 && use_side) encode_subframe(w, side, 1, bs, P, win, info ? &info[c] : NULL, 33);
         else encode_subframe(w, xin + c, nch, bs, P, win, info ? &info[c] : NULL, 32);
     }
@@ -685,6 +791,8 @@ static void encode_frame(bitw_t *w, const int32_t *xin, int nch, int bs, uint64_
     bw_put(w, c, 16);
     if (info)
         for (int k = 0; k < nch; ++k) info[k].nbytes = (int32_t)((w->nbits >> 3) - frame_start);
+    if (TR)
+        for (int k = 0; k < nch; ++k) TR[k].nbytes = (int32_t)((w->nbits >> 3) - frame_start);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -805,6 +913,30 @@ int oracle_encode_stream_info_i64(const int64_t *data, int64_t stream_size, uint
     free(b);
     return e;
 }
+
+/* the decision trace of one stream: recs[frame * nch + channel], see oracle_trace_rec */
+static int encode_stream_trace(const int32_t *data, int nch, int64_t stream_size, uint32_t level, oracle_trace_rec *recs) {
+    if (level > 8 || stream_size <= 0) return ERROR_INVALID_LEVEL;
+    crc_init();
+    enc_params_t P = level_params(level);
+    int64_t nf = (stream_size + P.blocksize - 1) / P.blocksize;
+    memset(recs, 0, sizeof(oracle_trace_rec) * (size_t)(nf * nch));
+    uint8_t *b = NULL;
+    int64_t nb = 0;
+    g_trace = recs;
+    int e = encode_stream(data, nch, stream_size, level, &b, &nb, NULL);
+    g_trace = NULL;
+    g_tcur = NULL;
+    free(b);
+    return e;
+}
+int oracle_encode_stream_trace(const int32_t *data, int64_t stream_size, uint32_t level, oracle_trace_rec *recs) {
+    return encode_stream_trace(data, 1, stream_size, level, recs);
+}
+int oracle_encode_stream_trace_i64(const int64_t *data, int64_t stream_size, uint32_t level, oracle_trace_rec *recs) {
+    return encode_stream_trace((const int32_t *)data, 2, stream_size, level, recs);
+}
+int oracle_trace_rec_size(void) { return (int)sizeof(oracle_trace_rec); }
 
 void oracle_free(void *p) { free(p); }
 

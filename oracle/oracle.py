@@ -26,6 +26,23 @@ class FrameInfo(ctypes.Structure):
     ]
 
 
+class TraceRec(ctypes.Structure):
+    """oracle_trace_rec: FrameInfo's fields plus the cause of every encoder decision (flac_oracle.c)."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in (
+        "type", "order", "porder", "wasted", "shift", "precision", "nbytes", "blocksize", "bps", "is_const", "fixed_valid",
+        "fixed_order", "lpc_tried", "lpc_drop", "quant_rc", "lev_usable", "lev_neg", "lev_zero", "lpc_order", "prec_before",
+        "prec_after", "raw_shift", "clamp_qmax", "clamp_qmin", "cand_type", "rice_min", "rice_max", "rice2", "rice_clamp30",
+        "row_over", "exact_over", "verbatim_cause", "channel", "nch", "st_fits", "st_small", "st_right_zero", "st_tried",
+        "st_use_side", "st_fit_sign",
+    )] + [(k, ctypes.c_int64) for k in ("st_est_left", "st_est_side", "est_bits", "exact_bits", "verbatim_bits")] + [("cmax", ctypes.c_double)]
+
+
+# lpc_drop and verbatim_cause codes (the TR_LPC_* / TR_VERB_* enums of flac_oracle.c)
+LPC_WON, LPC_NOT_TRIED, LPC_LAGS_ZERO, LPC_CMAX, LPC_QUANT_RC, LPC_PREC, LPC_RESIDUAL, LPC_RICE, LPC_ESTIMATE = range(9)
+VERB_NONE, VERB_SHORT, VERB_NO_CANDIDATE, VERB_ROW_CAP, VERB_EXACT = range(5)
+
+
 def _src_hash():
     import hashlib
 
@@ -68,39 +85,51 @@ def lib():
                 "oracle/liboracle.so is missing or stale: run oracle.build() (or __graft_entry__.build()) "
                 "before any GPU work; it is never built lazily"
             )
-        L = ctypes.CDLL(os.path.join(_HERE, "liboracle.so"))
-        i64, i32p, u8p = ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
-        i64p, f32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_float)
-        L.oracle_encode_i32.argtypes = [i32p, i64, i64, ctypes.c_uint32, i64p, i64p, ctypes.POINTER(u8p), ctypes.c_int]
-        L.oracle_encode_i32.restype = ctypes.c_int
-        L.oracle_decode_i32.argtypes = [u8p, i64p, i64p, i64, i64, i64, i64, i32p, ctypes.c_int]
-        L.oracle_decode_i32.restype = ctypes.c_int
-        L.oracle_float32_to_int32.argtypes = [f32p, i64, i64, f32p, i32p, f32p, f32p]
-        L.oracle_float32_to_int32.restype = ctypes.c_int
-        L.oracle_int32_to_float32.argtypes = [i32p, i64, i64, f32p, f32p, f32p]
-        L.oracle_int32_to_float32.restype = None
-        L.oracle_encode_stream_info.argtypes = [i32p, i64, ctypes.c_uint32, ctypes.POINTER(FrameInfo)]
-        L.oracle_encode_stream_info.restype = ctypes.c_int
-        f64p = ctypes.POINTER(ctypes.c_double)
-        L.oracle_encode_i64.argtypes = [i64p, i64, i64, ctypes.c_uint32, i64p, i64p, ctypes.POINTER(u8p), ctypes.c_int]
-        L.oracle_encode_i64.restype = ctypes.c_int
-        L.oracle_decode_i64.argtypes = [u8p, i64p, i64p, i64, i64, i64, i64, i64p, ctypes.c_int]
-        L.oracle_decode_i64.restype = ctypes.c_int
-        L.oracle_float64_to_int64.argtypes = [f64p, i64, i64, f64p, i64p, f64p, f64p]
-        L.oracle_float64_to_int64.restype = ctypes.c_int
-        L.oracle_int64_to_float64.argtypes = [i64p, i64, i64, f64p, f64p, f64p]
-        L.oracle_int64_to_float64.restype = None
-        L.oracle_encode_stream_info_i64.argtypes = [i64p, i64, ctypes.c_uint32, ctypes.POINTER(FrameInfo)]
-        L.oracle_encode_stream_info_i64.restype = ctypes.c_int
-        L.oracle_free.argtypes = [ctypes.c_void_p]
-        L.oracle_tukey_window.argtypes = [ctypes.c_int, f32p]
-        L.oracle_det_log2.argtypes = [ctypes.c_double]
-        L.oracle_det_log2.restype = ctypes.c_double
-        L.oracle_num_threads.restype = ctypes.c_int
-        L.oracle_set_threads.argtypes = [ctypes.c_int]
-        L.oracle_set_threads.restype = None
-        _LIB = L
+        _LIB = load(os.path.join(_HERE, "liboracle.so"))
     return _LIB
+
+
+def load(path):
+    """Load a build of flac_oracle.c and declare its exports (lib() loads oracle/liboracle.so; tools/oracle_branch_coverage.py
+    an instrumented build)."""
+    L = ctypes.CDLL(path)
+    i64, i32p, u8p = ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
+    i64p, f32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_float)
+    L.oracle_encode_i32.argtypes = [i32p, i64, i64, ctypes.c_uint32, i64p, i64p, ctypes.POINTER(u8p), ctypes.c_int]
+    L.oracle_encode_i32.restype = ctypes.c_int
+    L.oracle_decode_i32.argtypes = [u8p, i64p, i64p, i64, i64, i64, i64, i32p, ctypes.c_int]
+    L.oracle_decode_i32.restype = ctypes.c_int
+    L.oracle_float32_to_int32.argtypes = [f32p, i64, i64, f32p, i32p, f32p, f32p]
+    L.oracle_float32_to_int32.restype = ctypes.c_int
+    L.oracle_int32_to_float32.argtypes = [i32p, i64, i64, f32p, f32p, f32p]
+    L.oracle_int32_to_float32.restype = None
+    L.oracle_encode_stream_info.argtypes = [i32p, i64, ctypes.c_uint32, ctypes.POINTER(FrameInfo)]
+    L.oracle_encode_stream_info.restype = ctypes.c_int
+    f64p = ctypes.POINTER(ctypes.c_double)
+    L.oracle_encode_i64.argtypes = [i64p, i64, i64, ctypes.c_uint32, i64p, i64p, ctypes.POINTER(u8p), ctypes.c_int]
+    L.oracle_encode_i64.restype = ctypes.c_int
+    L.oracle_decode_i64.argtypes = [u8p, i64p, i64p, i64, i64, i64, i64, i64p, ctypes.c_int]
+    L.oracle_decode_i64.restype = ctypes.c_int
+    L.oracle_float64_to_int64.argtypes = [f64p, i64, i64, f64p, i64p, f64p, f64p]
+    L.oracle_float64_to_int64.restype = ctypes.c_int
+    L.oracle_int64_to_float64.argtypes = [i64p, i64, i64, f64p, f64p, f64p]
+    L.oracle_int64_to_float64.restype = None
+    L.oracle_encode_stream_info_i64.argtypes = [i64p, i64, ctypes.c_uint32, ctypes.POINTER(FrameInfo)]
+    L.oracle_encode_stream_info_i64.restype = ctypes.c_int
+    L.oracle_encode_stream_trace.argtypes = [i32p, i64, ctypes.c_uint32, ctypes.POINTER(TraceRec)]
+    L.oracle_encode_stream_trace.restype = ctypes.c_int
+    L.oracle_encode_stream_trace_i64.argtypes = [i64p, i64, ctypes.c_uint32, ctypes.POINTER(TraceRec)]
+    L.oracle_encode_stream_trace_i64.restype = ctypes.c_int
+    L.oracle_trace_rec_size.restype = ctypes.c_int
+    assert L.oracle_trace_rec_size() == ctypes.sizeof(TraceRec)
+    L.oracle_free.argtypes = [ctypes.c_void_p]
+    L.oracle_tukey_window.argtypes = [ctypes.c_int, f32p]
+    L.oracle_det_log2.argtypes = [ctypes.c_double]
+    L.oracle_det_log2.restype = ctypes.c_double
+    L.oracle_num_threads.restype = ctypes.c_int
+    L.oracle_set_threads.argtypes = [ctypes.c_int]
+    L.oracle_set_threads.restype = None
+    return L
 
 
 def _p(a, t):
@@ -249,6 +278,30 @@ def stream_info(x, level=5):
     if err != 0:
         raise RuntimeError(f"Encoding failed, return code = {err}")
     return [{k: getattr(i, k) for k, _ in FrameInfo._fields_} for i in infos]
+
+
+def _stream_trace(x, level, nch):
+    x = np.ascontiguousarray(x, dtype=np.int64 if nch == 2 else np.int32).reshape(-1)
+    bs = 1152 if level <= 2 else 4096
+    nf = (x.shape[0] + bs - 1) // bs
+    recs = (TraceRec * (nch * nf))()
+    if nch == 2:
+        err = lib().oracle_encode_stream_trace_i64(_p(x, ctypes.c_int64), x.shape[0], level, recs)
+    else:
+        err = lib().oracle_encode_stream_trace(_p(x, ctypes.c_int32), x.shape[0], level, recs)
+    if err != 0:
+        raise RuntimeError(f"Encoding failed, return code = {err}")
+    return [{k: getattr(r, k) for k, _ in TraceRec._fields_} for r in recs]
+
+
+def stream_trace(x, level=5):
+    """Per-frame decision trace of one 1-D int32 stream: stream_info's keys plus the cause of each decision."""
+    return _stream_trace(x, level, 1)
+
+
+def stream_trace_i64(x, level=5):
+    """Per-SUBFRAME decision trace of one 1-D int64 stream: entry [2 * frame + channel]."""
+    return _stream_trace(x, level, 2)
 
 
 def tukey_window(n):
