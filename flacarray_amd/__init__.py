@@ -24,6 +24,7 @@ from .libflacarray import (
     float32_to_int32_device,
     float64_to_int64_device,
     md5_device,
+    overwrite_flac_device,
     set_decode_verify,
     set_encode_md5,
     set_encode_verify,
@@ -41,6 +42,7 @@ __all__ = [
     "FlacArray",
     "DeviceDecodeIndex",
     "append_flac_device",
+    "overwrite_flac_device",
     "array_compress",
     "array_decompress",
     "array_decompress_slice",

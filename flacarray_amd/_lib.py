@@ -44,6 +44,12 @@ SYMBOLS = [
     "fa_append_capacity_bytes_i64",
     "fa_append_i32_device",
     "fa_append_i64_device",
+    "fa_overwrite_workspace_bytes",
+    "fa_overwrite_workspace_bytes_i64",
+    "fa_overwrite_capacity_bytes",
+    "fa_overwrite_capacity_bytes_i64",
+    "fa_overwrite_i32_device",
+    "fa_overwrite_i64_device",
     "fa_quantise_f32_device",
     "fa_quantise_f64_device",
     "fa_float64_to_int64_device",
@@ -163,6 +169,15 @@ def lib():
         getattr(L, name).restype = i64
     for name in ("fa_append_i32_device", "fa_append_i64_device"):
         getattr(L, name).argtypes = [vp, i64, vp, vp, i64, i64, vp, i64, u32, vp, i64, vp, i64, vp, vp, pi64, vp]
+        getattr(L, name).restype = cint
+    for name in ("fa_overwrite_workspace_bytes", "fa_overwrite_workspace_bytes_i64"):
+        getattr(L, name).argtypes = [i64, i64, i64, i64, i64, u32]
+        getattr(L, name).restype = i64
+    for name in ("fa_overwrite_capacity_bytes", "fa_overwrite_capacity_bytes_i64"):
+        getattr(L, name).argtypes = [i64, i64, i64, i64, i64, i64, u32]
+        getattr(L, name).restype = i64
+    for name in ("fa_overwrite_i32_device", "fa_overwrite_i64_device"):
+        getattr(L, name).argtypes = [vp, i64, vp, vp, i64, i64, vp, i64, vp, i64, i64, u32, vp, i64, vp, i64, vp, vp, pi64, vp]
         getattr(L, name).restype = cint
     for name in ("fa_quantise_f32_device", "fa_quantise_f64_device"):
         getattr(L, name).argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]

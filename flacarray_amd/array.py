@@ -401,6 +401,26 @@ class FlacArray:
         first = compare_flac_device(comp, st, nb, x.reshape(self._st.count, self._stream_size), off, gain)
         return first.cpu().numpy().reshape(self._leading_shape)
 
+    def _splice_layout(self, level, what):
+        """The layout a splice (append, overwrite) needs, checked on the host copy: STREAMINFO with the block size of
+        `level`, then the SEEKTABLE (last) of one point per frame.  Returns (blob, starts, nbytes) as flat numpy arrays."""
+        st = self._st
+        B = 1152 if level <= 2 else 4096
+        blob = np.asarray(st.blob, dtype=np.uint8)
+        s0 = np.asarray(st.starts, dtype=np.int64).reshape(-1)
+        nb = np.asarray(st.nbytes_per_stream, dtype=np.int64).reshape(-1)
+        if np.any(nb < 46) or np.any(s0 < 0) or np.any(s0 + nb > blob.size):
+            raise ValueError("the store's stream index does not fit its compressed bytes")
+        at = lambda k: blob[s0 + k].astype(np.int64)  # noqa: E731
+        bs = (at(8) << 8) | at(9)
+        stl = (at(43) << 16) | (at(44) << 8) | at(45)
+        if np.any(at(4) != 0) or np.any(at(42) != 0x83) or np.any(stl != 18 * (-(-st.samples // np.maximum(bs, 1)))):
+            raise ValueError(f"{what} needs streams written by this library (a SEEKTABLE with one point per frame); "
+                             "libFLAC-written streams are not supported")
+        if np.any(bs != B):
+            raise ValueError(f"level {level} has block size {B}, the store's streams have {int(bs[bs != B][0])}: {what} at the store's level")
+        return blob, s0, nb
+
     def append(self, data, level=5, verify=None, md5=False):
         """Extend every stream by data.shape[-1] samples, in place; returns self (addition to the reference API).
 
@@ -446,21 +466,7 @@ class FlacArray:
         n = shape[-1]
         if n == 0:
             return self.sign() if md5 else self
-        # the layout the splice needs, checked on the host copy: STREAMINFO, then the SEEKTABLE (last) of one point per frame
-        B = 1152 if level <= 2 else 4096
-        blob = np.asarray(st.blob, dtype=np.uint8)
-        s0 = np.asarray(st.starts, dtype=np.int64).reshape(-1)
-        nb = np.asarray(st.nbytes_per_stream, dtype=np.int64).reshape(-1)
-        if np.any(nb < 46) or np.any(s0 < 0) or np.any(s0 + nb > blob.size):
-            raise ValueError("the store's stream index does not fit its compressed bytes")
-        at = lambda k: blob[s0 + k].astype(np.int64)  # noqa: E731
-        bs = (at(8) << 8) | at(9)
-        stl = (at(43) << 16) | (at(44) << 8) | at(45)
-        if np.any(at(4) != 0) or np.any(at(42) != 0x83) or np.any(stl != 18 * (-(-st.samples // np.maximum(bs, 1)))):
-            raise ValueError("append needs streams written by this library (a SEEKTABLE with one point per frame); "
-                             "libFLAC-written streams are not supported")
-        if np.any(bs != B):
-            raise ValueError(f"level {level} has block size {B}, the store's streams have {int(bs[bs != B][0])}: append at the store's level")
+        blob, s0, nb = self._splice_layout(level, "append")
         if verify is None:
             verify = _encode_verify_default()
         res = self._resident
@@ -481,6 +487,95 @@ class FlacArray:
         ishape = np.shape(st.starts)
         new = _Store.build(tuple(st.shape[:-1]) + (st.samples + n,), None, st.dtype, comp2.cpu().numpy(),
                            starts2.cpu().numpy().reshape(ishape), nbytes2.cpu().numpy().reshape(ishape), st.offsets, st.gains, st.dist)
+        if res is not None:
+            if res.get("index") is not None:
+                res["index"].close()
+            self._resident = dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), index=None)
+        self._st = new
+        return self.sign() if md5 else self
+
+    def overwrite(self, first, data, streams=None, level=5, verify=None, md5=False):
+        """Replace samples [first, first + n) of every stream, or of the streams named, in place; returns self (addition
+        to the reference API; `__setitem__` keeps raising).
+
+        `data`: a numpy array or a torch tensor on the device, of this array's dtype.  `streams=None`: shape
+        leading_shape + (n,) ((n,) for a 1-D array).  Otherwise `streams` is a 1-D integer array of flat C-order stream
+        indices and `data` is (len(streams), n), row j for stream streams[j]; an index out of range or named twice raises
+        ValueError and an empty `streams` does nothing.  0 <= first and first + n <= stream_size are required (ValueError:
+        growing the store is append's job); n == 0 does nothing.  Integer arrays: with y the decoded array after
+        y[streams, first:first+n] = data, the store (every byte of `compressed`, `stream_starts`, `stream_nbytes`) is the
+        one from_array(y, level=level) writes, after any sequence of overwrites and appends -- provided `level` is the
+        level the store was written at (a level of another block size raises ValueError).  Float arrays: the new samples
+        are quantised with the store's own `stream_offsets` and `stream_gains`, which do not change (a NaN raises
+        RuntimeError, out-of-range values become INT_MIN): the store is the integer encode of the patched integers.
+
+        Only the frames that overlap the range are decoded, patched and encoded again; the frames in front of them are
+        copied verbatim, the frames behind them verbatim at their new place, with their seek points moved
+        (overwrite_flac_device); each call copies the whole compressed blob once.  Residency follows append: a resident
+        array stays resident, with an exact-size copy of the new blob and its decode index rebuilt on next use; any other
+        array uploads its store, patches it on the device and brings the result back.  The store is replaced, not
+        changed: a FlacArray(self) copy made before still holds the old one.  `verify`: decode the re-encoded span and
+        compare it with its input on the device before returning (None = the default of set_encode_verify).  Streams
+        without this library's SEEKTABLE (libFLAC-written) raise ValueError; a store assembled by `dist` raises
+        NotImplementedError.
+
+        A stream that takes part comes out UNSIGNED (its STREAMINFO MD5 zeroed: its samples changed); a stream that does
+        not keeps its header, and so a valid signature, verbatim.  `md5=True` is overwrite followed by sign()."""
+        import torch
+
+        from .libflacarray import _encode_verify_default, overwrite_flac_device
+
+        st = self._st
+        if st.global_shape != st.grid:
+            raise NotImplementedError("overwrite is not supported for a store that is one part of a distributed array")
+        is_tensor = isinstance(data, torch.Tensor)
+        dt = np.dtype(str(data.dtype).replace("torch.", "")) if is_tensor else np.asarray(data).dtype
+        if dt != st.dtype:
+            raise ValueError(f"data of dtype {dt} does not match the array's dtype {st.dtype}")
+        shape = tuple(int(k) for k in data.shape)
+        idx = None
+        if streams is None:
+            if len(shape) != len(st.shape) or shape[:-1] != tuple(st.shape[:-1]):
+                raise ValueError(f"data of shape {shape} does not match the array's leading shape {tuple(st.shape[:-1])}")
+        else:
+            idx = streams.detach().cpu().numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
+            if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+                raise ValueError("streams should be a 1-D array of integer stream indices")
+            idx = idx.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= st.count):
+                raise ValueError(f"streams holds an index outside [0, {st.count})")
+            if np.unique(idx).size != idx.size:
+                raise ValueError("streams names a stream twice")
+            if len(shape) != 2 or shape[0] != idx.size:
+                raise ValueError(f"data of shape {shape} does not match the shape ({idx.size}, n) of {idx.size} streams to overwrite")
+        if level < 0 or level > 8:
+            raise ValueError("FLAC only supports compression levels 0-8")
+        n = shape[-1]
+        first = int(first)
+        if first < 0 or first + n > st.samples:
+            raise ValueError(f"samples [{first}, {first + n}) do not lie inside streams of {st.samples} samples (append grows the store)")
+        if n == 0 or (idx is not None and idx.size == 0):
+            return self.sign() if md5 else self
+        blob, s0, nb = self._splice_layout(level, "overwrite")
+        if verify is None:
+            verify = _encode_verify_default()
+        res = self._resident
+        if res is not None:
+            dev = res["device"]
+            comp, starts, nbytes, off, gain = res["compressed"], res["starts"], res["nbytes"], res["offsets"], res["gains"]
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            up = lambda a, t: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=t).reshape(-1)).to(dev)  # noqa: E731
+            ft = np.float64 if st.wide else np.float32
+            comp, starts, nbytes = up(blob, np.uint8), up(s0, np.int64), up(nb, np.int64)
+            off, gain = up(st.offsets, ft), up(st.gains, ft)
+        x = data.to(dev) if is_tensor else torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+        x = x.reshape(st.count if idx is None else idx.size, n).contiguous()
+        comp2, starts2, nbytes2 = overwrite_flac_device(comp, starts, nbytes, st.samples, first, x, streams=idx, level=level, offsets=off,
+                                                        gains=gain, verify=verify, compact=res is not None)
+        ishape = np.shape(st.starts)
+        new = _Store.build(tuple(st.shape), None, st.dtype, comp2.cpu().numpy(), starts2.cpu().numpy().reshape(ishape),
+                           nbytes2.cpu().numpy().reshape(ishape), st.offsets, st.gains, st.dist)
         if res is not None:
             if res.get("index") is not None:
                 res["index"].close()

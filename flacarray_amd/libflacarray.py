@@ -1482,3 +1482,129 @@ def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, o
         _, digests = check_md5_device(out[0], out[1], out[2], stream_size + n, is_int64=wide, return_digests=True)
         sign_streams_device(out[0], out[1], digests)
     return out
+
+
+def overwrite_flac_device(compressed, starts, nbytes, stream_size, first, data, streams=None, level=5, offsets=None, gains=None, verify=False,
+                          compact=False):
+    """Replace samples [first, first + n) of some or all streams of a device-resident store, n = data.shape[-1]: returns
+    the new (compressed, starts, nbytes), all on the device, the store's arguments left as they are.
+
+    The store must have this library's layout (one SEEKTABLE point per frame) and `level` the level it was written at
+    (its block size is checked against the streams' STREAMINFO).  `streams=None`: every stream takes part, `data` is a
+    C-contiguous tensor on the store's device of shape (n_stream, n) or starts.shape + (n,) ((n,) for one stream).
+    Otherwise `streams` is a 1-D integer array or tensor of flat (C-order) stream indices and `data` is (len(streams), n),
+    row j for stream streams[j]; an index out of range or named twice raises ValueError, no stream does nothing.  int32
+    data for one-channel streams, int64 for two-channel streams; or float32 / float64 with the store's `offsets` and `gains`
+    (one per stream of the STORE), which then quantise it exactly as the encoder quantises (quantise_rows_kernel: a NaN
+    raises RuntimeError, out-of-range values become INT_MIN).  0 <= first and first + n <= stream_size, else ValueError;
+    n == 0 does nothing.
+
+    The result is byte for byte the encode of the patched integers (fa_overwrite_i32_device / fa_overwrite_i64_device,
+    include/flacarray_hip.h), except the STREAMINFO MD5: a stream that takes part gets a zero one (its samples changed), a
+    stream that does not is copied whole and keeps its own.  Only the frames that overlap the range are decoded and encoded
+    again; all other bytes of the store are copied once.  `compressed` is a view of a buffer sized for the worst case;
+    `compact=True` returns an exact-size copy instead.  A participating stream whose STREAMINFO names another block size,
+    channel count or stream size than the call's raises ValueError before anything is decoded.  `verify=True`: decode the
+    re-encoded span of the participating streams from the result and compare it with the patched old span; a difference
+    raises RuntimeError."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64 or starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes should be int64 tensors of one shape")
+    if level < 0 or level > 8:
+        raise ValueError("FLAC only supports compression levels 0-8")
+    n_stream = int(np.prod(starts.shape))
+    if data.dim() == 0:
+        raise ValueError("data needs a stream axis")
+    n = int(data.shape[-1])
+    idx = None
+    if streams is None:
+        m = n_stream
+        if tuple(data.shape) not in ((n_stream, n), tuple(starts.shape) + (n,)) and not (data.dim() == 1 and n_stream == 1):
+            raise ValueError(f"data of shape {tuple(data.shape)} does not match {n_stream} streams (starts of shape {tuple(starts.shape)})")
+    else:
+        idx = streams.detach().cpu().numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
+        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+            raise ValueError("streams should be a 1-D array of integer stream indices")
+        idx = idx.astype(np.int64)
+        m = int(idx.size)
+        if m and (idx.min() < 0 or idx.max() >= n_stream):
+            raise ValueError(f"streams holds an index outside [0, {n_stream})")
+        if np.unique(idx).size != m:
+            raise ValueError("streams names a stream twice")
+        if tuple(data.shape) != (m, n):
+            raise ValueError(f"data of shape {tuple(data.shape)} does not match {m} streams to overwrite")
+    is_float = data.dtype in (torch.float32, torch.float64)
+    if data.dtype not in (torch.int32, torch.int64) and not is_float:
+        raise ValueError(f"Unsupported data type '{data.dtype}': int32, int64, float32 or float64")
+    if is_float != (offsets is not None) or (offsets is None) != (gains is None):
+        raise ValueError("float data need the store's offsets and gains, integer data take neither")
+    first = int(first)
+    if first < 0 or first + n > stream_size:
+        raise ValueError(f"samples [{first}, {first + n}) do not lie inside streams of {stream_size} samples")
+    dev = compressed.device
+    if not (compressed.is_cuda and data.device == dev and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("overwrite_flac_device needs compressed, starts, nbytes and data on the same GPU")
+    if n == 0 or m == 0:
+        return compressed, starts, nbytes
+    wide = data.dtype in (torch.int64, torch.float64)
+    L = _lib.lib()
+    data = data.reshape(m, n).contiguous()
+    with _on_device(dev):
+        d_idx = None if idx is None else torch.from_numpy(idx).to(dev)
+        if is_float:
+            off = offsets.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+            gain = gains.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+            if off.numel() != n_stream or gain.numel() != n_stream:
+                raise ValueError("offsets and gains need one value per stream")
+            if d_idx is not None:
+                off, gain = off[d_idx].contiguous(), gain[d_idx].contiguous()
+            ints = torch.empty((m, n), dtype=torch.int64 if wide else torch.int32, device=dev)
+            errcode = (L.fa_quantise_f64_device if wide else L.fa_quantise_f32_device)(
+                _dp(data), m, n, _dp(off), _dp(gain), _dp(ints), n, _stream_ptr())
+            if errcode & _lib.ERROR_NAN_INPUT:
+                raise RuntimeError("Cannot convert data with NaNs to integers")
+            if errcode != 0:
+                raise RuntimeError(f"Quantisation failed, return code = {errcode}")
+            data = ints
+        comp = compressed.contiguous()
+        st, nb = starts.reshape(-1).contiguous(), nbytes.reshape(-1).contiguous()
+        ws_bytes = (L.fa_overwrite_workspace_bytes_i64 if wide else L.fa_overwrite_workspace_bytes)(n_stream, stream_size, m, first, n, level)
+        cap = (L.fa_overwrite_capacity_bytes_i64 if wide else L.fa_overwrite_capacity_bytes)(comp.numel(), n_stream, stream_size, m, first, n, level)
+        if ws_bytes < 0 or cap < 0:
+            raise RuntimeError("Overwriting failed: invalid geometry")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        buf = torch.empty(cap, dtype=torch.uint8, device=dev)
+        index = torch.empty(2 * n_stream, dtype=torch.int64, device=dev)
+        total = ctypes.c_int64(0)
+        errcode = (L.fa_overwrite_i64_device if wide else L.fa_overwrite_i32_device)(
+            _dp(comp), comp.numel(), _dp(st), _dp(nb), n_stream, stream_size, _dp(d_idx), m, _dp(data), first, n, level, _dp(ws), ws_bytes,
+            _dp(buf), cap, _dp(index[:n_stream]), _dp(index[n_stream:]), ctypes.byref(total), _stream_ptr())
+    if errcode == 8192:  # FA_ERROR_DECODE_INIT
+        raise ValueError("Overwriting needs streams written by this library (a SEEKTABLE with one point per frame) with the block size of "
+                         f"level {level}, {2 if wide else 1} channel(s) ({data.dtype} data) and {stream_size} samples")
+    if errcode != 0:
+        raise RuntimeError(f"Overwriting failed, return code = {errcode}")
+    blob = buf[: total.value]
+    if compact:
+        blob = blob.clone()
+        del buf
+    out = (blob, index[:n_stream].reshape(starts.shape), index[n_stream:].reshape(starts.shape))
+    if verify:
+        B = 1152 if level <= 2 else 4096
+        lo = first // B * B
+        hi = min(-(-(first + n) // B) * B, stream_size)
+        rows = slice(None) if d_idx is None else d_idx
+        span = decode_flac_device(out[0], index[:n_stream][rows], index[n_stream:][rows], stream_size, lo, hi, is_int64=wide,
+                                  verify=True).reshape(m, -1)
+        if lo == first and hi == first + n:
+            want = data
+        else:
+            want = decode_flac_device(comp, st[rows], nb[rows], stream_size, lo, hi, is_int64=wide).reshape(m, -1).clone()
+            want[:, first - lo : first - lo + n] = data
+        bad = (span != want).any(dim=1)
+        if bool(bad.any()):
+            at = torch.where(bad, (span != want).int().argmax(dim=1) + lo, torch.full_like(bad, -1, dtype=torch.int64))
+            _raise_on_mismatch(at)
+    return out

@@ -210,6 +210,43 @@ int fa_append_i64_device(const unsigned char* d_old, int64_t n_old_bytes, const 
                          int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
                          int64_t* h_total_bytes, void* stream);
 
+/* Overwrite: replace samples [first, first + n) of m streams of a device-resident store (written by this library: one
+ * SEEKTABLE point per frame) by d_data[m][n] -- int32 for one-channel streams (fa_overwrite_i32_device), int64 for
+ * two-channel streams (fa_overwrite_i64_device) -- so that the result is, byte for byte, what fa_encode_i32_device /
+ * fa_encode_i64_device writes for the patched samples (same level: its block size must be the one in the streams' STREAMINFO),
+ * except that a stream which does not take part is copied whole, its STREAMINFO MD5 included, while a stream which takes part
+ * gets a zero MD5.  d_stream_index[m]: the flat indices of the streams that take part, row j of d_data belonging to stream
+ * d_stream_index[j]; NULL (with m == n_stream): all streams, in order.  With B the level's block size, F the frames per
+ * stream, f0 = first / B and f1 = min(F, ceil((first + n) / B)): the span [f0 B, min(f1 B, stream_size)) of the m streams is
+ * decoded (not when the range is the whole span), the new samples are laid over it, the (m, span) image is encoded, and one
+ * splice kernel writes the result: per participating stream the header, the seek points and frames in front of the span
+ * verbatim, the new frames renumbered k -> f0 + k (as fa_append_*_device renumbers), the frames behind the span verbatim and
+ * their seek points with the offset moved.  Requires 0 <= first, n > 0, first + n <= stream_size
+ * (FA_ERROR_DECODE_SAMPLE_RANGE) and 0 < m <= n_stream.  d_old is 16-byte aligned and unchanged; the caller owns it, d_data,
+ * d_stream_index, the workspace (fa_overwrite_workspace_bytes[_i64]: the integer image, the encode's blob and its own
+ * workspace) and d_bytes (fa_overwrite_capacity_bytes[_i64] bytes: the old blob, the span encode's worst case and 6 bytes per
+ * new frame; a smaller buffer gives FA_ERROR_ALLOC if the result does not fit, nothing outside it written).  The result is
+ * d_bytes[0, *h_total_bytes), d_starts, d_nbytes [n_stream].  The call waits on `stream` for the check, the span decode and
+ * the total; the splice may still be queued when it returns: d_bytes / d_starts / d_nbytes are complete, and the workspace is
+ * free again, when `stream` reaches the end of the call's work.  Before anything is decoded or encoded: FA_ERROR_DECODE_SEEK
+ * for a stream index outside [0, n_stream) or named twice; FA_ERROR_DECODE_INIT for a participating stream without this
+ * encoder's SEEKTABLE, whose STREAMINFO names another block size, channel count (1 for the _i32 call, 2 for the _i64 call)
+ * or total sample count than stream_size, or whose seek offsets of frames f0 and f1 are not ordered inside its body. */
+int64_t fa_overwrite_workspace_bytes(int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level);
+int64_t fa_overwrite_workspace_bytes_i64(int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level);
+int64_t fa_overwrite_capacity_bytes(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n,
+                                    uint32_t level);
+int64_t fa_overwrite_capacity_bytes_i64(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n,
+                                        uint32_t level);
+int fa_overwrite_i32_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                            int64_t n_stream, int64_t stream_size, const int64_t* d_stream_index, int64_t m, const int32_t* d_data,
+                            int64_t first, int64_t n, uint32_t level, void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes,
+                            int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream);
+int fa_overwrite_i64_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                            int64_t n_stream, int64_t stream_size, const int64_t* d_stream_index, int64_t m, const int64_t* d_data,
+                            int64_t first, int64_t n, uint32_t level, void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes,
+                            int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream);
+
 /* Quantisation with GIVEN per-stream offsets and gains (the inner loop of float32_to_int32 / float64_to_int64, utils.c:229-240
  * and :316-323, without the range pass): d_output[s * out_stride + i] for d_input[n_stream][n]; out_stride >= n lets the caller
  * write into a wider image.  What an append to a float store quantises its new samples with.  FA_ERROR_NAN_INPUT for a NaN
@@ -411,7 +448,7 @@ const char* fa_version(void);
  * do not / process default, see fa_set_decode_verify; revision 3 added the std entry points, revision 4 the compare entry
  * points and fa_set_encode_verify); a binding built against
  * another revision must refuse the library instead of calling it with a shifted argument list --
- * flacarray_amd/_lib.py does. */
+ * flacarray_amd/_lib.py does.  Entry points that are only added (the append, MD5 and overwrite groups) leave it as it is. */
 #define FA_ABI_VERSION 4  /* (revision 4: fa_compare_i32_device / fa_compare_i64_device / fa_set_encode_verify) */
 int fa_abi_version(void);
 
