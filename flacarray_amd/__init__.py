@@ -6,7 +6,7 @@ Drop-in names of the reference (hpc4cmb/flacarray): `array_compress`, `array_dec
 BASELINE.json.  All compute runs in hand-written HIP kernels (libflacarray_hip.so); there is
 no CPU fallback.
 """
-from .array import FlacArray
+from .array import FlacArray, StreamStats
 from .compress import array_compress
 from .decompress import array_decompress, array_decompress_slice
 from .libflacarray import (
@@ -25,6 +25,7 @@ from .libflacarray import (
     float64_to_int64_device,
     md5_device,
     overwrite_flac_device,
+    reduce_flac_device,
     set_decode_verify,
     set_encode_md5,
     set_encode_verify,
@@ -40,6 +41,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "FlacArray",
+    "StreamStats",
     "DeviceDecodeIndex",
     "append_flac_device",
     "overwrite_flac_device",
@@ -56,6 +58,7 @@ __all__ = [
     "decode_flac_device",
     "decode_slices_device",
     "compare_flac_device",
+    "reduce_flac_device",
     "md5_device",
     "check_md5_device",
     "sign_streams_device",

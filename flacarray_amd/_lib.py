@@ -71,6 +71,9 @@ SYMBOLS = [
     "fa_sign_streams_device",
     "fa_check_md5_device",
     "fa_set_encode_md5",
+    "fa_reduce_i32_device",
+    "fa_reduce_i64_device",
+    "fa_reduce_indexed",
     "fa_encode_f32_host",
     "fa_encode_f64_host",
     "fa_decode_f32_host",
@@ -224,6 +227,12 @@ def lib():
     L.fa_sign_streams_device.restype = cint
     L.fa_check_md5_device.argtypes = [vp, i64, vp, vp, i64, i64, cint, i64, vp, vp, vp, cint]
     L.fa_check_md5_device.restype = cint
+    L.fa_reduce_i32_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, cint]
+    L.fa_reduce_i32_device.restype = cint
+    L.fa_reduce_i64_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, cint]
+    L.fa_reduce_i64_device.restype = cint
+    L.fa_reduce_indexed.argtypes = [vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, cint]
+    L.fa_reduce_indexed.restype = cint
     L.fa_set_encode_md5.argtypes = [cint]
     L.fa_set_encode_md5.restype = cint
     L.fa_profile_enable.argtypes = [cint]

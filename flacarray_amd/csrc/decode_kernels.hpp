@@ -500,14 +500,16 @@ struct DecodeArgs {
     const int64_t* task_first;    // slice first sample (stream coordinates)
     const int64_t* task_last;     // slice end (exclusive)
     const int64_t* task_out_off;  // output element offset of the slice's first sample
-    // outputs
-    int32_t* out_i32;
-    float* out_f32;         // when non-null: dequantised output instead of out_i32
-    const float* offsets;   // per stream
-    const float* gains;
+    // outputs.  (The unions: the reducing sink, which has no use for the store's, the restore's, the two-channel image's or
+    // the compare sink's arguments, keeps its own in their places -- the layout, and with it the code of every other
+    // instantiation, is what it was without that sink.)
+    union { int32_t* out_i32; long long* red_min; };
+    union { float* out_f32; long long* red_max; };                 // when non-null: dequantised output instead of out_i32
+    union { const float* offsets; long long* red_sum; };           // per stream
+    union { const float* gains; unsigned long long* red_sq_hi; };
     int* err;
     // two-channel arrays (NCH == 2): out_i32 is then the task-local planar image
-    uint32_t* hibits;   // [n_tasks][2][hib_words] bit 32 of every sample
+    union { uint32_t* hibits; unsigned long long* red_sq_lo; };   // [n_tasks][2][hib_words] bit 32 of every sample
     int32_t* assign;    // [n_tasks] channel assignment once both subframes are decoded, else -1
     int32_t hib_words;  // ceil(B / 32)
     int32_t verbatim_done;  // NCH == 2: VERBATIM first subframes (no wasted bits) were decoded by verbatim_channel0_kernel
@@ -515,8 +517,13 @@ struct DecodeArgs {
     // caller's samples stand where the output would be -- int32 / int64, or float32 / float64 quantised with `offsets` /
     // `gains` first -- and first_mismatch[stream] receives the smallest sample index that differs (atomicMin; all ones,
     // i.e. -1 as int64, where nothing differs)
-    const void* cmp;
-    unsigned long long* first_mismatch;
+    // reducing sink (decode_frames_kernel<..., RED = true>; one channel): the samples [first, last) of every row are cut
+    // into red_nbins bins of red_width samples (the last one may be short) and each bin's min, max, sum and the two
+    // radix-2^32 limbs of its sum of squares land in red_*[row * red_nbins + bin].  Grid mode: row = stream; list mode:
+    // task_out_off carries row * red_nbins.  The arrays hold the identities (INT64_MAX, INT64_MIN, 0) before the launch;
+    // red_sq_hi / red_sq_lo may be null together.
+    union { const void* cmp; int64_t red_width; };
+    union { unsigned long long* first_mismatch; int64_t red_nbins; };
 };
 
 // ------------------------------------------------------------------------------------------
@@ -768,7 +775,12 @@ __device__ __noinline__ BitsRet slow_sample(const uint8_t* cbase, const uint8_t*
 // float32 input quantised with the row's offset and gain (quantise_f32, the encoder's own arithmetic) -- and compared
 // with the decoded integers; a lane that finds a difference lowers a.first_mismatch[stream] to its first differing
 // sample.  Matching data issue no atomics.  Two channels keep the planar image, which compare_channels_kernel compares.
-template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false>
+// RED (one channel, integers): the reducing sink.  Nothing is stored: the lane folds each sample it decodes (wasted bits
+// restored, inside its valid range [lo, hi)) into a running min / max / sum / sum of squares held in registers, and
+// writes them out at every bin boundary it crosses and at the end of its range -- with plain 8-byte stores when the bin
+// lies wholly inside the lane's range (it then has no other contributor), with 64-bit atomics onto the pre-set
+// identities when two frames share it.  No tile image, no cooperative store, no row table.
+template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false>
 #ifndef FA_K7_WAVES_ATTR
 #define FA_K7_WAVES_ATTR
 #endif
@@ -779,9 +791,10 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     constexpr int kTileG = kTileW / 4;
     constexpr int kTileSwz = 32 / kTileG;
     static_assert(NCH == 1 || (kTileW == 32 && !F32), "two-channel variant: 32-sample tiles, integer output");
+    static_assert(!RED || (NCH == 1 && !F32 && !CMP), "reducing sink: one channel, integer domain");
     constexpr bool SINK = CMP && NCH == 1;  // the tile store compares instead of writing
     // one LDS object, so that the ring image starts at LDS address 0 (ring_words builds its addresses with an OR)
-    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + kTileW * kLaneStride + (F32 ? 128 : 0)];
+    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + (RED ? 0 : kTileW * kLaneStride) + (F32 ? 128 : 0)];
     uint32_t* const rings = lds_k7;
     int32_t* const tile = reinterpret_cast<int32_t*>(lds_k7 + kDecRingWords * kLaneStride);  // sample t of lane l at t*64 + (l ^ 8*(t>>2))
     float2* const row_fg = reinterpret_cast<float2*>(lds_k7 + kDecRingWords * kLaneStride + kTileW * kLaneStride);
@@ -805,7 +818,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         } else {
             s = task / a.nfr; f = a.f0 + (task - s * a.nfr);
             sl_first = a.first; sl_last = a.first + a.n_decode;
-            out_off = s * a.n_decode;
+            if constexpr (RED) out_off = s * a.red_nbins;
+            else out_off = s * a.n_decode;
         }
     }
     const int64_t fstart = f * (int64_t)a.B;
@@ -924,6 +938,12 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     int plen = 4, esc = 15, ps = 0, pleft = 0, k = 0, escw = -1;
     uint32_t kp1 = 1;  // k + 1: the bits a code takes beyond its zeros (0 for a lane that consumes nothing, see below)
     uint32_t hbw = 0;  // NCH == 2: bit 32 (the sign) of the samples of the current tile
+    // RED: the piece [red_seg, red_end) of bin red_bin that lies inside [lo, hi) (frame coordinates) and what it holds so far
+    int red_seg = 0, red_end = 0;
+    int64_t red_bin = 0;
+    int32_t red_mn = INT32_MAX, red_mx = INT32_MIN;
+    int64_t red_sm = 0;
+    uint64_t red_qh = 0, red_ql = 0;
 
     if (task_live) {
         bool is_lpc = false;
@@ -957,9 +977,11 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             // ---- warm-up samples, predictor description, residual header (serial per lane) ----
             for (int i = 0; i < order; ++i) {
                 const double x = get_wide(bps);
-                if (i < kTileW) {
-                    tile[i * kLaneStride + (lane ^ ((i >> 2) * kTileSwz))] = wrap32(x);  // (wasted bits are restored in flush_tile)
-                    if constexpr (NCH == 2) hbw |= (x < 0.0) ? (1u << i) : 0u;
+                if constexpr (!RED) {  // (the reducing sink takes the warm-up samples from the history, in the sample loop)
+                    if (i < kTileW) {
+                        tile[i * kLaneStride + (lane ^ ((i >> 2) * kTileSwz))] = wrap32(x);  // (wasted bits are restored in flush_tile)
+                        if constexpr (NCH == 2) hbw |= (x < 0.0) ? (1u << i) : 0u;
+                    }
                 }
 #pragma unroll
                 for (int jj = 0; jj < MO; ++jj)
@@ -1003,6 +1025,15 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             if (h2 > bs) h2 = bs;
             lo = (int)l;
             hi = (int)(h2 > l ? h2 : l);
+            if constexpr (RED) {
+                if (hi > lo) {  // the bin of the lane's first sample, and where it ends in this frame
+                    const int64_t g = fstart - sl_first;  // (frame start in range coordinates; may be negative)
+                    red_bin = (g + lo) / a.red_width;
+                    const int64_t e = (red_bin + 1) * a.red_width - g;
+                    red_seg = lo;
+                    red_end = (int)(e < hi ? e : hi);
+                }
+            }
         }
     }
     // A VERBATIM first subframe (no wasted bits) is a run of fixed-width fields: verbatim_channel0_kernel has decoded it
@@ -1067,13 +1098,14 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     __builtin_amdgcn_wave_barrier();
     int64_t row0;  // output element index of frame sample 0
     if constexpr (NCH == 2) row0 = (task * 2 + chn) * (int64_t)a.B;
+    else if constexpr (RED) row0 = 0;  // (no rows: out_off is the lane's first bin slot)
     else row0 = out_off + (fstart - sl_first);
     // The store pass `it` of a tile has this lane write a piece of row it * (64 / kTileG) + lane / kTileG: that
     // row's output offset is fetched from its owner lane once per frame and kept in registers (no LDS table:
     // the LDS saved is what lets more waves share a CU); the valid range is fetched in the rare clipped path.
     int64_t rout[kTileG];
 #pragma unroll
-    for (int it = 0; it < kTileG; ++it) {
+    for (int it = 0; it < (RED ? 0 : kTileG); ++it) {
         const int r = it * (64 / kTileG) + (lane / kTileG);
         const uint32_t rl = (uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)(uint32_t)(uint64_t)row0);
         const uint32_t rh = (uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)(uint32_t)((uint64_t)row0 >> 32));
@@ -1133,6 +1165,48 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         return (uint32_t)(lim < 32 ? (lim > 0 ? lim : 0) : 32);
     };
     uint32_t zlim = (escw < 0) ? zlim_for(k) : 0u;
+
+    // reducing sink: write the lane's finished piece of a bin, then open the next one
+    const int red_w = (int)(a.red_width < 65536 ? a.red_width : 65536);  // (a step past any frame's end is as good as the width)
+    auto red_emit = [&]() __attribute__((always_inline)) {
+        const int64_t o = out_off + red_bin;
+        const int64_t b0 = sl_first + red_bin * a.red_width;  // the bin in stream coordinates
+        const int64_t b1 = (b0 + a.red_width < sl_last) ? b0 + a.red_width : sl_last;
+        if (fstart + red_seg == b0 && fstart + red_end == b1) {  // the whole bin: no other frame holds a sample of it
+            a.red_min[o] = red_mn;
+            a.red_max[o] = red_mx;
+            a.red_sum[o] = red_sm;
+            if (a.red_sq_hi) { a.red_sq_hi[o] = red_qh; a.red_sq_lo[o] = red_ql; }
+        } else {
+            (void)__hip_atomic_fetch_min(a.red_min + o, (long long)red_mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            (void)__hip_atomic_fetch_max(a.red_max + o, (long long)red_mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            (void)__hip_atomic_fetch_add(a.red_sum + o, (long long)red_sm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (a.red_sq_hi) {
+                (void)__hip_atomic_fetch_add(a.red_sq_hi + o, (unsigned long long)red_qh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(a.red_sq_lo + o, (unsigned long long)red_ql, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        red_mn = INT32_MAX; red_mx = INT32_MIN; red_sm = 0; red_qh = 0; red_ql = 0;
+        red_bin++;
+        red_seg = red_end;
+        red_end = (red_end + red_w < hi) ? red_end + red_w : hi;
+    };
+    // sample i of the lane's frame (wasted bits not yet restored).  The boundary test is wave-wide first: bins of a frame
+    // and more cross one in a few samples per frame
+    auto red_take = [&](int i, int32_t x0) __attribute__((always_inline)) {
+        if ((uint32_t)(i - lo) < (uint32_t)(hi - lo)) {
+            const int32_t x = (int32_t)((uint32_t)x0 << wasted);
+            red_mn = x < red_mn ? x : red_mn;
+            red_mx = x > red_mx ? x : red_mx;
+            red_sm += x;
+            const uint64_t q = (uint64_t)((int64_t)x * (int64_t)x);  // <= 2^62
+            red_ql += (uint32_t)q;
+            red_qh += q >> 32;
+        }
+        if (__builtin_expect(__any(i + 1 == red_end), 0)) {
+            if (i + 1 == red_end) red_emit();
+        }
+    };
 
     // one sample of every lane.  GUARD: lanes may be in warm-up or past their frame's end.
     // PART: a partition boundary may fall inside this macro step (decided once per step for the wave)
@@ -1279,13 +1353,22 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             }
 #endif
             h[u % MO] = xd;
+            if constexpr (RED) {
+                red_take(i, wrap32(xd));
+            } else {
 #if (FA_K7_X & 4)
             if (u == 0)
 #endif
             tile[u * kLaneStride + (lane ^ ((u >> 2) * kTileSwz))] = wrap32(xd);
+            }
         } else if constexpr (GUARD) {
+            if constexpr (RED) {
+                // every warm-up sample (i < order <= MO): its value sits in the history, slot i % MO = u % MO
+                if (i < bs) red_take(i, wrap32(h[u % MO]));
+            } else {
             // warm-up sample 16..31 (orders above 16): its value sits in the history
             if (i < bs && i >= kTileW) tile[u * kLaneStride + (lane ^ ((u >> 2) * kTileSwz))] = wrap32(h[u % MO]);
+            }
         }
     };
 
@@ -1320,6 +1403,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
 
     // cooperative store of the tile: (64 / kTileG) rows x kTileW samples per pass, 16 bytes per lane
     auto flush_tile = [&](int tbase) __attribute__((always_inline)) {
+        if constexpr (RED) return;  // (no tile)
         __builtin_amdgcn_wave_barrier();
         if constexpr (NCH == 2) {
             // bit 32 of this lane's 32 samples (tiles are 32 samples wide)

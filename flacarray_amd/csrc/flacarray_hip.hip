@@ -40,6 +40,7 @@
 #include "append_kernels.hpp"
 #include "overwrite_kernels.hpp"
 #include "md5_kernels.hpp"
+#include "reduce_kernels.hpp"
 
 namespace {
 
@@ -58,15 +59,17 @@ using namespace fa;
 // device share its cached scratch buffers); calls that target different devices -- one process driving several
 // GPUs from several threads -- do not serialise each other.  g_mu guards the map of device states only.
 constexpr int kProfPairs = 6;
+constexpr int kScratchSlots = 17;
 struct DeviceState {
     std::recursive_mutex api_mu;
     std::map<int, float*> windows;  // blocksize -> device tukey(0.5) table
     uint16_t* crc_tab = nullptr;
     uint16_t* crc_tab_fused = nullptr;
     // [10]: K1a partial ranges; [12]: std chunk sums and means, [13]: std summation plans (fa_stream_std_*_device);
-    // [14]: the MD5 check's decoded column chunk, [15]: its chaining states, digests and flags (fa_check_md5_device)
-    void* scratch[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // [14]: the MD5 check's decoded column chunk, [15]: its chaining states, digests and flags (fa_check_md5_device);
+    // [16]: the binned reduction's decoded column chunk (fa_reduce_*)
+    void* scratch[kScratchSlots] = {};
+    size_t scratch_bytes[kScratchSlots] = {};
     uint64_t scratch_epoch = 1;  // bumped whenever a scratch slot is (re)allocated or released: cached contents are then stale
     // frame-header table of the most recent encode geometry (host copy + what the device copy was built from)
     std::vector<uint4> h_hdr;
@@ -511,6 +514,27 @@ struct DecodeIndex {
     int device = -1;
 };
 
+// The reducing sink of K7 (fa_reduce_*, one channel): bins of `width` samples over the decoded range, the rows of the
+// result being all streams (sel == nullptr) or the n_sel streams a device array names; the bin arrays hold the identities.
+struct ReduceSink {
+    int64_t width, nbins, n_sel;
+    const int64_t* sel;
+    ReduceOut out;
+};
+
+// device memory for a task table: the index's own (grown on demand) or the cached scratch
+int task_table_mem(DecodeIndex* idx, size_t bytes, void** out) {
+    if (!idx) return get_scratch(3, bytes, out);
+    if (idx->tasks_bytes < bytes) {
+        if (idx->tasks) (void)hipFree(idx->tasks);
+        idx->tasks = nullptr; idx->tasks_bytes = 0;
+        FA_HIP_TRY(hipMalloc(&idx->tasks, bytes + 4096));
+        idx->tasks_bytes = bytes + 4096;
+    }
+    *out = idx->tasks;
+    return FA_ERROR_NONE;
+}
+
 // idx == nullptr: parse + index into the cached scratch, then decode (one-off calls).
 // idx != nullptr, build_only: parse + index into buffers owned by *idx, no decode.
 // idx != nullptr, !build_only: decode with the index (d_bytes / d_starts / d_nbytes are not looked at).
@@ -521,15 +545,19 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
                        const float* d_gains, hipStream_t st, int nch = 1, int64_t* d_out_i64 = nullptr, double* d_out_f64 = nullptr,
                        const double* d_offsets64 = nullptr, const double* d_gains64 = nullptr, DecodeIndex* idx = nullptr,
                        bool build_only = false, int verify = -1, void* h_copy = nullptr, size_t h_copy_bytes = 0,
-                       bool* h_copied = nullptr, const void* d_cmp = nullptr, int64_t* d_first_mismatch = nullptr) {
+                       bool* h_copied = nullptr, const void* d_cmp = nullptr, int64_t* d_first_mismatch = nullptr,
+                       const ReduceSink* red = nullptr) {
     // compare sink (d_first_mismatch != null): whole streams through K7 in grid mode, the caller's samples at d_cmp in place
     // of an output (float32 / float64 when offsets / gains are given); a frame that is rejected or cannot be located marks
     // its stream instead of setting the error word, so only errors of the stream headers are returned
     const bool cmp = (d_first_mismatch != nullptr);
 #ifdef FA_DEV_MINIMAL
-    if (cmp) return FA_ERROR_CONVERT_TYPE;
+    if (cmp || red) return FA_ERROR_CONVERT_TYPE;
 #endif
     if (cmp) verify = 0;
+    // reducing sink (red != null, one channel): the range in grid mode over all streams, or in list mode over the streams
+    // named -- the bin arrays stand where the output would be, and errors are the plain decode's
+    if (red && (nch != 1 || cmp)) return FA_ERROR_CONVERT_TYPE;
     int rc = FA_ERROR_NONE;
     int h_err[4] = {0, 0, 0, 0};
     bool err_cleared = true;  // (the one-off path clears them before K6)
@@ -679,18 +707,7 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
             }
         }
         void* pl = nullptr;
-        if (use_index) {
-            if (idx->tasks_bytes < 5 * stp) {
-                if (idx->tasks) (void)hipFree(idx->tasks);
-                idx->tasks = nullptr; idx->tasks_bytes = 0;
-                FA_HIP_TRY(hipMalloc(&idx->tasks, 5 * stp + 4096));
-                idx->tasks_bytes = 5 * stp + 4096;
-            }
-            pl = idx->tasks;
-        } else {
-            rc = get_scratch(3, 5 * stp, &pl);
-            if (rc) return rc;
-        }
+        if ((rc = task_table_mem(use_index ? idx : nullptr, 5 * stp, &pl))) return rc;
         char* c = reinterpret_cast<char*>(pl);
         if (inl.n == 0) {
             FA_HIP_TRY(hipMemcpyAsync(c, h.data(), 5 * stp, hipMemcpyHostToDevice, st));
@@ -707,10 +724,18 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         a.task_out_off = reinterpret_cast<const int64_t*>(c + 4 * stp);
     }
     if (a.B > kMaxBlock * 16) return FA_ERROR_DECODE_INIT;
+    if (red) {
+        if (n_slices >= 0) return FA_ERROR_CONVERT_TYPE;
+        a.red_min = red->out.mn; a.red_max = red->out.mx; a.red_sum = red->out.sum;
+        a.red_sq_hi = red->out.sq_hi; a.red_sq_lo = red->out.sq_lo;
+        a.red_width = red->width; a.red_nbins = red->nbins;
+        if (red->sel) a.n_tasks = red->n_sel * a.nfr;  // list mode; the table is built on the device, below
+        if (a.n_tasks <= 0 || a.n_tasks > (int64_t)64 * 0x7fffffff) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    }
     const unsigned nblk = (unsigned)((a.n_tasks + 63) / 64);
     const bool f32 = cmp ? (d_offsets != nullptr) : (d_out_f32 != nullptr);
     const bool f64 = (d_out_f64 != nullptr);
-    if (!cmp && a.B <= kLatMaxBlock && latency_allowed(a.n_tasks)) {
+    if (!cmp && !red && a.B <= kLatMaxBlock && latency_allowed(a.n_tasks)) {
         LatWide wd;
         wd.out_i64 = d_out_i64; wd.out_f64 = d_out_f64; wd.offsets = d_offsets64; wd.gains = d_gains64;
         auto launch_latency = [&](const DecodeArgs& aa, int* flag) {
@@ -797,6 +822,18 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         FA_HIP_TRY(hipStreamSynchronize(st));
         tasks_uploaded = true;
     }
+    if (red && red->sel) {
+        // K7's task table for the named streams: task t = (row t / nfr, frame f0 + t % nfr), output slot row * nbins
+        const size_t stp = align_up((size_t)a.n_tasks * 8, 256);
+        void* pl = nullptr;
+        if ((rc = task_table_mem(use_index ? idx : nullptr, 5 * stp, &pl))) return rc;
+        int64_t* t5[5];
+        for (int k = 0; k < 5; ++k) t5[k] = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(pl) + k * stp);
+        hipLaunchKernelGGL(reduce_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, red->sel, n_stream, a.n_tasks, a.nfr,
+                           a.f0, a.first, a.first + a.n_decode, red->nbins, t5[0], t5[1], t5[2], t5[3], t5[4], d_err,
+                           (int)FA_ERROR_DECODE_SAMPLE_RANGE);
+        a.task_stream = t5[0]; a.task_frame = t5[1]; a.task_first = t5[2]; a.task_last = t5[3]; a.task_out_off = t5[4];
+    }
 #ifndef FA_DEV_MINIMAL
     if (nch == 2) {
         // two-channel arrays: task-local planar image (low words), bit 32 of every sample, task status
@@ -861,7 +898,8 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     const bool verifying_k7 = (verify < 0 ? g_verify.load() : verify != 0);
     const bool beside = verifying_k7 && a.n_tasks >= 16384 && std::getenv("FLACARRAY_HIP_VERIFY_AFTER") == nullptr &&
                         run_verify_beside_begin(st);
-    if (cmp) {
+    if (red) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    else if (cmp) {
         if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -875,14 +913,16 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
     if (h_err[1] & kFlagNeed16) {
-        if (cmp) {
+        if (red) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (cmp) {
             if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
             else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     }
     if (h_err[1] & kFlagNeed32) {
-        if (cmp) {
+        if (red) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (cmp) {
             if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
             else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -1051,7 +1091,7 @@ int fa_device_count(void) {
 
 void fa_release_scratch(void) {
     FA_API_LOCK_OR(return);
-    for (int i = 0; i < 16; ++i) {
+    for (int i = 0; i < kScratchSlots; ++i) {
         if (ds_->scratch[i]) (void)hipFree(ds_->scratch[i]);
         ds_->scratch[i] = nullptr;
         ds_->scratch_bytes[i] = 0;
@@ -2272,6 +2312,128 @@ int fa_check_md5_device(const unsigned char* d_bytes, int64_t n_bytes, const int
     FA_HIP_TRY(hipStreamSynchronize(st));  // (the scratch is free again, d_status / d_digests are complete)
     FA_HIP_TRY(hipGetLastError());
     return FA_ERROR_NONE;
+}
+
+// ---- binned reduction: min / max / sums of the decoded samples, without a decoded copy -----------------------------
+// One-channel streams: the reducing sink of K7, at every width (profiles/reduce.md).  Two-channel streams: decoded column
+// chunks of whole frames under a cap, each folded into the bins by the chunk reducers.
+// the block size in stream 0's STREAMINFO (chunks are cut at frame boundaries; a header that does not say costs speed only)
+static int reduce_peek_blocksize(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, hipStream_t st, int64_t* B) {
+    *B = 4096;
+    int64_t s0 = -1;
+    FA_HIP_TRY(hipMemcpyAsync(&s0, d_starts, 8, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    if (s0 < 0 || s0 + 12 > n_bytes) return FA_ERROR_NONE;
+    unsigned char h[12];
+    FA_HIP_TRY(hipMemcpyAsync(h, d_bytes + s0, 12, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    const int64_t bmin = ((int64_t)h[8] << 8) | h[9], bmax = ((int64_t)h[10] << 8) | h[11];
+    if (std::memcmp(h, "fLaC", 4) == 0 && bmin == bmax && bmin >= 16) *B = bmin;
+    return FA_ERROR_NONE;
+}
+
+static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                         int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel,
+                         const int64_t* d_sel, int64_t max_temp_bytes, int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi,
+                         uint64_t* d_sq_lo, void* stream, int verify) {
+    FA_API_LOCK;
+    if (ix) {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess || cur != ix->device) return FA_ERROR_DEVICE;
+        if (ix->nch != nch) return FA_ERROR_DECODE_INIT;
+        n_stream = ix->n_stream; stream_size = ix->stream_size; d_bytes = ix->bytes; n_bytes = ix->n_bytes;
+    } else if (!d_bytes || !d_starts || !d_nbytes) {
+        return FA_ERROR_CONVERT_TYPE;
+    }
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
+    if (first < 0 && last < 0) { first = 0; last = stream_size; }
+    if (first < 0 || last > stream_size || first >= last) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    if (width < 1 || !d_min || !d_max || !d_sum || (d_sq_hi == nullptr) != (d_sq_lo == nullptr) || (nch == 2 && d_sq_hi)) return FA_ERROR_CONVERT_TYPE;
+    if (d_sel && n_sel <= 0) return n_sel == 0 ? FA_ERROR_NONE : FA_ERROR_CONVERT_TYPE;
+    const int64_t n = last - first;
+    if (width > n) width = n;
+    const int64_t nbins = (n + width - 1) / width;
+    const int64_t rows = d_sel ? n_sel : n_stream;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ReduceSink red;
+    red.width = width; red.nbins = nbins; red.n_sel = n_sel; red.sel = d_sel;
+    red.out.mn = reinterpret_cast<long long*>(d_min); red.out.mx = reinterpret_cast<long long*>(d_max);
+    red.out.sum = reinterpret_cast<long long*>(d_sum);
+    red.out.sq_hi = reinterpret_cast<unsigned long long*>(d_sq_hi); red.out.sq_lo = reinterpret_cast<unsigned long long*>(d_sq_lo);
+    red.out.nbins = nbins;
+    const int64_t cells = rows * nbins;
+    if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
+    hipLaunchKernelGGL(reduce_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, red.out, cells);
+    if (nch == 1)
+        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, n, -1, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr, 0,
+                                  nullptr, nullptr, nullptr, &red);
+    int rc;
+    int64_t B = ix ? ix->B : 0;
+    if (!ix && (rc = reduce_peek_blocksize(d_bytes, n_bytes, d_starts, st, &B))) return rc;
+    const int64_t sample_bytes = 8;
+    const int64_t cap = max_temp_bytes > 0 ? max_temp_bytes : (int64_t)FA_REDUCE_TEMP_BYTES;
+    int64_t cw = cap / (rows * sample_bytes) / B * B;
+    if (cw < B) cw = B;
+    void* d_tmp = nullptr;
+    if ((rc = get_scratch(16, (size_t)rows * (size_t)std::min(cw, n) * (size_t)sample_bytes + 256, &d_tmp))) return rc;
+    std::vector<int64_t> sl;  // named streams: the chunk as one slice per row (host arrays: stream | first | count | output offset)
+    if (d_sel) {
+        sl.resize(4 * (size_t)rows);
+        FA_HIP_TRY(hipMemcpyAsync(sl.data(), d_sel, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
+        FA_HIP_TRY(hipStreamSynchronize(st));
+    }
+    for (int64_t at = first; at < last;) {
+        const int64_t end = std::min(last, at / B * B + cw);  // (chunks after the first start at a frame)
+        const int64_t w = end - at;
+        if (d_sel)
+            for (int64_t r = 0; r < rows; ++r) { sl[rows + r] = at; sl[2 * rows + r] = w; sl[3 * rows + r] = r * w; }
+        rc = decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, at, w, d_sel ? rows : -1, d_sel ? sl.data() : nullptr,
+                                d_sel ? sl.data() + rows : nullptr, d_sel ? sl.data() + 2 * rows : nullptr, d_sel ? sl.data() + 3 * rows : nullptr,
+                                nullptr, nullptr, nullptr, nullptr, st, 2, reinterpret_cast<int64_t*>(d_tmp), nullptr, nullptr, nullptr, ix, false,
+                                verify);
+        if (rc) return rc;
+        if (width >= 64) {
+            const int64_t nseg = (w + kReduceSeg - 1) / kReduceSeg;
+            if (rows * nseg > 0x7fffffff) return FA_ERROR_ALLOC;
+            const dim3 grid((unsigned)(rows * nseg)), block(64);
+            hipLaunchKernelGGL(reduce_wave_kernel, grid, block, 0, st, reinterpret_cast<const long long*>(d_tmp), w, at, first, last, width, nseg, red.out);
+        } else {
+            const int64_t bin_lo = (at - first) / width, n_bin = (end - 1 - first) / width - bin_lo + 1;
+            const int64_t nblk = (n_bin + 255) / 256;
+            if (rows * nblk > 0x7fffffff) return FA_ERROR_ALLOC;
+            const dim3 grid((unsigned)(rows * nblk)), block(256);
+            hipLaunchKernelGGL(reduce_lane_kernel, grid, block, 0, st, reinterpret_cast<const long long*>(d_tmp), w, at, first, last, width, bin_lo, n_bin, nblk,
+                               red.out);
+        }
+        at = end;
+    }
+    FA_HIP_TRY(hipStreamSynchronize(st));  // (the scratch is free again, the bins are complete)
+    FA_HIP_TRY(hipGetLastError());
+    return FA_ERROR_NONE;
+}
+
+int fa_reduce_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                         int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams,
+                         int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify) {
+    return reduce_device(1, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, width, n_sel, d_sel_streams, 0, d_min,
+                         d_max, d_sum, d_sq_hi, d_sq_lo, stream, verify);
+}
+
+int fa_reduce_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                         int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams,
+                         int64_t max_temp_bytes, int64_t* d_min, int64_t* d_max, int64_t* d_sum, void* stream, int verify) {
+    return reduce_device(2, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, width, n_sel, d_sel_streams,
+                         max_temp_bytes, d_min, d_max, d_sum, nullptr, nullptr, stream, verify);
+}
+
+int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                      int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify) {
+    DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
+    if (!ix) return FA_ERROR_DECODE_INIT;
+    return reduce_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, width, n_sel, d_sel_streams, max_temp_bytes, d_min, d_max,
+                         d_sum, d_sq_hi, d_sq_lo, stream, verify);
 }
 
 int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t stream_size, const float* d_quanta,

@@ -1210,6 +1210,120 @@ def decode_slices_device(compressed, starts, nbytes, stream_size, slice_stream, 
     return out, out_off
 
 
+def _reduce_args(n_stream, stream_size, width, first_sample, last_sample, streams):
+    """The argument checks of the binned reduction (ValueError, before anything touches the GPU).  Returns (first, last,
+    width, nbins, stream indices as an int64 numpy array or None)."""
+    stream_size = int(stream_size)
+    if stream_size <= 0:
+        raise ValueError("You must specify the non-zero stream size")
+    first = int(first_sample)
+    last = stream_size if last_sample is None else int(last_sample)
+    if first < 0 or last > stream_size or first >= last:
+        raise ValueError(f"samples [{first}, {last}) are not a non-empty range inside streams of {stream_size} samples")
+    n = last - first
+    if width is None:
+        width = n
+    width = int(width)
+    if width < 1:
+        raise ValueError("width should be at least one sample")
+    width = min(width, n)
+    idx = None
+    if streams is not None:
+        torch = _torch()
+        idx = streams.detach().cpu().numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
+        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+            raise ValueError("streams should be a 1-D array of integer stream indices")
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= n_stream):
+            raise ValueError(f"streams holds an index outside [0, {n_stream})")
+        if np.unique(idx).size != idx.size:
+            raise ValueError("streams names a stream twice")
+    return first, last, width, -(-n // width), idx
+
+
+def _reduce_outputs(rows, nbins, wide, dev):
+    torch = _torch()
+    mk = lambda: torch.empty((rows, nbins), dtype=torch.int64, device=dev)  # noqa: E731
+    return mk(), mk(), mk(), (None if wide else mk()), (None if wide else mk())
+
+
+def reduce_flac_device(compressed, starts, nbytes, stream_size, width=None, first_sample=0, last_sample=None, streams=None,
+                       is_int64=False, verify=None, max_temp_bytes=None):
+    """Binned min / max / sum / sum of squares of what device-resident streams decode to, without a decoded copy
+    (fa_reduce_i32_device / fa_reduce_i64_device).  Samples [first_sample, last_sample) (default: everything) of every
+    stream, or of the streams that `streams` names (1-D flat indices, no repeats; rows come in that order), are cut into
+    nbins = ceil(n / width) bins of `width` samples, the last one possibly short; width=None is one bin.
+
+    Returns (min, max, sum, sumsq_hi, sumsq_lo): int64 device tensors of shape (rows, nbins) over the decoded INTEGERS
+    (for a float store the quantised ones).  min / max are exact; sum equals np.sum(x, dtype=np.int64) -- exact for
+    one-channel streams, modulo 2^64 for two-channel ones (is_int64); the limbs (None for two-channel streams) are the
+    exact sums of x*x mod 2^32 and x*x >> 32, so that the sum of squares is sumsq_hi * 2^32 + sumsq_lo.  An empty
+    `streams` returns tensors of shape (0, nbins).
+
+    One-channel streams are reduced inside the decoder, at about the cost of a decode and with nothing but the bins
+    written.  Two-channel streams go through decoded column chunks of whole frames that stay under `max_temp_bytes`
+    (default 256 MiB): that keeps the extra memory small but is SLOWER than decode_flac_device followed by torch
+    reductions when the whole decoded array would fit (at 1024 x 2^20 int64: 59 ms against 16; with a cap that holds the whole
+    range, 13 ms: profiles/reduce.md), because a chunk of few frames does not fill the decoder.  `verify` is the
+    decoder's frame CRC-16 check; argument errors raise ValueError before any GPU work, decode failures the decoder's
+    RuntimeError.  Streams of several block sizes are reduced one block size at a time."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64:
+        raise ValueError("starts and nbytes should be of type int64")
+    if starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes must have the same shape")
+    n_stream = int(np.prod(starts.shape))
+    if n_stream <= 0:
+        raise ValueError("starts needs at least one stream")
+    first, last, width, nbins, idx = _reduce_args(n_stream, stream_size, width, first_sample, last_sample, streams)
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("reduce_flac_device needs compressed, starts and nbytes on the same GPU")
+    rows = n_stream if idx is None else int(idx.size)
+    mn, mx, sm, qh, ql = _reduce_outputs(rows, nbins, is_int64, dev)
+    if rows == 0:
+        return mn, mx, sm, qh, ql
+    sel = None if idx is None else torch.from_numpy(idx).to(dev)
+    cap = 0 if max_temp_bytes is None else int(max_temp_bytes)
+    L = _lib.lib()
+    with _on_device(dev):
+        if is_int64:
+            errcode = L.fa_reduce_i64_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                             width, rows, _dp(sel), cap, _dp(mn), _dp(mx), _dp(sm), _stream_ptr(), _verify_arg(verify))
+        else:
+            errcode = L.fa_reduce_i32_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                             width, rows, _dp(sel), _dp(mn), _dp(mx), _dp(sm), _dp(qh), _dp(ql), _stream_ptr(),
+                                             _verify_arg(verify))
+    if errcode != 0:
+        # streams of different block sizes: one call per block size (see _blocksize_classes), rows scattered back
+        st, nb = starts.reshape(-1), nbytes.reshape(-1)
+        groups = None
+        if n_stream > 1 and bool(((st >= 0) & (nb >= 12) & (st + nb <= compressed.numel())).all()):
+            groups = _blocksize_classes(compressed[st[:, None] + torch.arange(12, device=dev)[None, :]].cpu().numpy())
+        if groups is None:
+            raise RuntimeError(f"Decoding failed, return code = {errcode}")
+        for g in groups:
+            if idx is None:
+                at, local = g, None
+            else:
+                at = np.flatnonzero(np.isin(idx, g))  # rows of the result that name a stream of this class
+                if at.size == 0:
+                    continue
+                local = np.searchsorted(g, idx[at])
+            gi = torch.from_numpy(g).to(dev)
+            part = reduce_flac_device(compressed, st[gi].contiguous(), nb[gi].contiguous(), stream_size, width, first, last, streams=local,
+                                      is_int64=is_int64, verify=verify, max_temp_bytes=max_temp_bytes)
+            ai = torch.from_numpy(at).to(dev)
+            for out, p in zip((mn, mx, sm, qh, ql), part):
+                if out is not None:
+                    out[ai] = p
+    return mn, mx, sm, qh, ql
+
+
 class DeviceDecodeIndex:
     """Decode index of one HBM-resident store (fa_decode_index_create): the stream headers are parsed and the byte
     offset of every frame is tabulated ONCE; `decode` / `decode_slices` then cost one kernel launch each.  Holds
@@ -1280,6 +1394,23 @@ class DeviceDecodeIndex:
         if errcode != 0:
             raise RuntimeError(f"Decoding failed, return code = {errcode}")
         return out
+
+    def reduce(self, width=None, first_sample=0, last_sample=None, streams=None, verify=None, max_temp_bytes=None):
+        """reduce_flac_device on the indexed store (fa_reduce_indexed): nothing is parsed again.  Returns (min, max, sum,
+        sumsq_hi, sumsq_lo), int64 tensors of shape (rows, nbins); the limbs are None for two-channel streams."""
+        torch = _torch()
+        first, last, width, nbins, idx = _reduce_args(self.n_stream, self.stream_size, width, first_sample, last_sample, streams)
+        rows = self.n_stream if idx is None else int(idx.size)
+        mn, mx, sm, qh, ql = _reduce_outputs(rows, nbins, self.is_int64, self.device)
+        if rows == 0:
+            return mn, mx, sm, qh, ql
+        sel = None if idx is None else torch.from_numpy(idx).to(self.device)
+        with _on_device(self.device):
+            errcode = self._L.fa_reduce_indexed(self._h, first, last, width, rows, _dp(sel), 0 if max_temp_bytes is None else int(max_temp_bytes),
+                                                _dp(mn), _dp(mx), _dp(sm), _dp(qh), _dp(ql), _stream_ptr(), _verify_arg(verify))
+        if errcode != 0:
+            raise RuntimeError(f"Decoding failed, return code = {errcode}")
+        return mn, mx, sm, qh, ql
 
     def decode_slices(self, slice_stream, slice_first, slice_count, offsets=None, gains=None, verify=None, to_host=False):
         """Batched random access (see decode_slices_device): returns (flat tensor, int64 numpy array of offsets);

@@ -382,6 +382,33 @@ int fa_compare_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const i
                           int64_t n_stream, int64_t stream_size, const void* d_data, const double* d_offsets, const double* d_gains,
                           int64_t* d_first_mismatch, void* stream);
 
+/* ---- Binned reduction: min, max, sum and sum of squares of the decoded integers, without a decoded copy.  Samples
+ * [first, last) of every stream (both negative: the whole stream) are cut into nbins = ceil((last - first) / width) bins
+ * [first + j * width, first + (j + 1) * width), the last one possibly short; a width beyond the range means one bin.  The
+ * rows of the result are all n_stream streams (d_sel_streams NULL; n_sel is then ignored) or the n_sel streams that the
+ * DEVICE array d_sel_streams names, in its order (an index outside [0, n_stream): FA_ERROR_DECODE_SAMPLE_RANGE; n_sel == 0
+ * does nothing).  Outputs, device, [rows][nbins] in C order: d_min / d_max (int64, exact), d_sum (int64: exact for
+ * one-channel streams, modulo 2^64 for two-channel ones, as a wrapping int64 sum is), and for one-channel streams
+ * d_sq_hi / d_sq_lo (NULL together: not wanted), the two exact limbs of the sum of squares in radix 2^32: d_sq_lo = sum of
+ * (x^2 mod 2^32), d_sq_hi = sum of (x^2 >> 32), sum of x^2 = d_sq_hi * 2^32 + d_sq_lo; exact below 2^32 samples per bin.
+ * What is reduced is what any FLAC decoder produces -- for float stores the quantised integers.
+ * One-channel streams are reduced inside the decoder (its store replaced by a sink that keeps each frame's running values
+ * in registers: nothing but the bins is written); two-channel streams go through decoded column chunks of whole frames
+ * that stay under max_temp_bytes (<= 0: FA_REDUCE_TEMP_BYTES; at least one frame of every row) -- a small cap saves memory
+ * and costs time, since a chunk of few frames does not fill the decoder (profiles/reduce.md).  `verify`, the error bits and
+ * the rule that all streams share one block size are the decode entry points'.  fa_reduce_indexed reduces the store of a
+ * decode index (either channel count; d_sq_hi / d_sq_lo NULL, and max_temp_bytes used, for two channels only) without
+ * parsing it again.  Everything is issued on `stream`, which is synchronised before returning. ---- */
+#define FA_REDUCE_TEMP_BYTES (256LL << 20)
+int fa_reduce_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                         int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams,
+                         int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
+int fa_reduce_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                         int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams,
+                         int64_t max_temp_bytes, int64_t* d_min, int64_t* d_max, int64_t* d_sum, void* stream, int verify);
+int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                      int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
+
 /* Batched random access: slice i is samples [first[i], first[i]+count[i]) of stream
  * slice_stream[i]; its samples are written at element offset out_offset[i] of the output.
  * The four slice arrays are HOST arrays of length n_slices.  The reference needs one
