@@ -274,19 +274,28 @@ def _metadata(rng, layout, frames, block, n):
     raise ValueError(layout)
 
 
-def write_stream(rng, n, block, channels=1, layout="libflac", sr_code=9, ss_code=7, kinds=None, bucket_cycle=False, cheap=False):
+def write_stream(rng, n, block, channels=1, layout="libflac", sr_code=9, ss_code=7, kinds=None, bucket_cycle=False, cheap=False,
+                 samples=None, bucket=None):
     """One stream of n samples (32 bps, 44.1 kHz, fixed block size `block`).  Mono: int32 samples.  Two channels:
     int64 samples packed as make_golden's g8-g13 (right << 32 | left as unsigned), the channel assignment drawn per
-    frame.  bucket_cycle: frame f takes an LPC order from ORDER_BUCKETS[f % 4].  cheap: CONSTANT / VERBATIM frames of
-    small values only.  Returns (samples, stream bytes, record)."""
+    frame.  bucket_cycle: frame f takes an LPC order from ORDER_BUCKETS[f % 4]; bucket: every frame takes one from
+    ORDER_BUCKETS[bucket].  cheap: CONSTANT / VERBATIM frames of small values only.  samples (mono only): the n int32
+    samples to code instead of drawn ones -- frame f codes samples[f * block : f * block + m]; the coding choices are
+    still drawn.  Returns (samples, stream bytes, record)."""
+    if samples is not None:
+        if channels != 1 or cheap:
+            raise ValueError("samples= is for one-channel streams with drawn coding")
+        samples = np.asarray(samples)
+        if samples.shape != (n,) or samples.dtype != np.int32:
+            raise ValueError("samples= needs %d int32 samples" % n)
     feats = Counter()
     sr_value = {12: 44, 13: 44100, 14: 4410}.get(sr_code, 0)
     frames, chans = [], []
     nf = (n + block - 1) // block
     for f in range(nf):
         m = min(block, n - f * block)
-        bucket = f % 4 if bucket_cycle else None
-        kk = ("lpc",) if bucket_cycle else kinds
+        bk = f % 4 if bucket_cycle else bucket
+        kk = ("lpc",) if bk is not None else kinds
         if cheap:
             v = int(rng.integers(-1000, 1000))
             if rng.random() < 0.9:
@@ -300,8 +309,8 @@ def write_stream(rng, n, block, channels=1, layout="libflac", sr_code=9, ss_code
             chans.append((x,))
             continue
         if channels == 1:
-            x = _segment(rng, m)
-            sub = code_channel(rng, x, 32, feats, kk, bucket)
+            x = _segment(rng, m) if samples is None else samples[f * block : f * block + m].astype(np.int64)
+            sub = code_channel(rng, x, 32, feats, kk, bk)
             frames.append(frame([0] * m, f, 32, sub, ss_code=ss_code, sr_code=sr_code, sr_value=sr_value))
             chans.append((x,))
         else:
@@ -309,7 +318,7 @@ def write_stream(rng, n, block, channels=1, layout="libflac", sr_code=9, ss_code
             asg = int(rng.choice([1, 8, 9, 10]))
             side, mid = left - right, (left + right) >> 1
             coded = {1: ((left, 32), (right, 32)), 8: ((left, 32), (side, 33)), 9: ((side, 33), (right, 32)), 10: ((mid, 32), (side, 33))}[asg]
-            subs = [code_channel(rng, c, b, feats, kk, bucket) for c, b in coded]
+            subs = [code_channel(rng, c, b, feats, kk, bk) for c, b in coded]
             feats["assignment_%d" % asg] += 1
             if np.abs(side).max() >= 2**31:
                 feats["side_33bit"] += 1

@@ -54,6 +54,19 @@ def range_params(x):
         return off, amp / f64(9223372036854775807)  # :287
 
 
+def quantise_with(x, offsets, gains):
+    """The per-sample step of float32_to_int32 (utils.c:234-240) / float64_to_int64 (utils.c:318-325) with the offsets
+    and gains given, one per row of x: subtract and multiply in x's type, +-0.5 in double, the truncating cast."""
+    x = np.asarray(x)
+    dt, bits = (f32, 32) if x.dtype == f32 else (f64, 64)
+    off, gain = np.asarray(offsets, dtype=dt).reshape(-1), np.asarray(gains, dtype=dt).reshape(-1)
+    with np.errstate(all="ignore"):
+        st = x - off[:, None]  # :234 / :318
+        pr = (gain[:, None] * st).astype(f64)  # :236/238 a float multiply for float32, then the double +-0.5
+        v = np.where(st >= 0, pr + 0.5, pr - 0.5)  # :319-323
+    return cvtt(v, bits)
+
+
 def float32_to_int32(x, quanta=None):
     """utils.c:159-243 -> (int32 [n_stream, n], offsets float32, gains float32)."""
     x = np.ascontiguousarray(x, dtype=f32).reshape(-1, np.shape(x)[-1])
@@ -63,10 +76,7 @@ def float32_to_int32(x, quanta=None):
         nquant = cvtt(off.astype(f64) / sq.astype(f64), 64)  # :221
         off = (sq.astype(f64) * nquant.astype(f64)).astype(f32)  # :222
         gain = np.where(sq == 0, f64(1.0), 1.0 / sq.astype(f64)).astype(f32)  # :224-230
-        st = x - off[:, None]  # :234, float
-        pr = (gain[:, None] * st).astype(f64)  # :236/238, float multiply, then the double +-0.5
-        v = np.where(st >= 0, pr + 0.5, pr - 0.5)
-    return cvtt(v, 32), off, gain
+    return quantise_with(x, off, gain), off, gain  # :234-240
 
 
 def float64_to_int64(x, quanta=None):
@@ -78,10 +88,7 @@ def float64_to_int64(x, quanta=None):
         nquant = cvtt(off / sq, 64)  # :305
         off = sq * nquant.astype(f64)  # :306
         gain = np.where(sq == 0, 1.0, 1.0 / sq)  # :308-314
-        t = x - off[:, None]  # :318
-        pr = gain[:, None] * t
-        v = np.where(t >= 0, pr + 0.5, pr - 0.5)  # :319-323
-    return cvtt(v, 64), off, gain
+    return quantise_with(x, off, gain), off, gain  # :318-325
 
 
 def int32_to_float32(ints, offsets, gains):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import quant_model as M
+from tests.compare_corpus import _frame_offsets, _header_bytes
 from tests.conftest import full_range_i32, sinusoid_noise_f32, sinusoid_noise_i32, strip_seektable
 
 pytestmark = pytest.mark.gpu
@@ -125,33 +126,6 @@ def test_compare_float_quanta(fa, torch, dtype, level, shape):
     assert sum(len(v) for v in same.values()) >= 4
     z2 = _mutate(x, same, lambda v: np.nextafter(v, dtype(np.inf)))
     assert (_compare(fa, torch, comp, st, nb, z2, off, gain) == -1).all()
-
-
-def _frame_offsets(seg):
-    """Byte offset of every frame of one stream, from its SEEKTABLE (one point per frame; placeholders skipped)."""
-    off, points = 4, []
-    while True:
-        last, typ = seg[off] >> 7, seg[off] & 0x7F
-        ln = int.from_bytes(bytes(seg[off + 1 : off + 4]), "big")
-        if typ == 3:
-            body = bytes(seg[off + 4 : off + 4 + ln])
-            for k in range(ln // 18):
-                if int.from_bytes(body[18 * k : 18 * k + 8], "big") != 2**64 - 1:
-                    points.append(int.from_bytes(body[18 * k + 8 : 18 * k + 16], "big"))
-        off += 4 + ln
-        if last:
-            return [off + p for p in points]
-
-
-def _header_bytes(seg, at):
-    """Length of the frame header at `at`, CRC-8 included (RFC 9639 9.1)."""
-    assert seg[at] == 0xFF and seg[at + 1] == 0xF8
-    bsc, src, u0 = seg[at + 2] >> 4, seg[at + 2] & 15, seg[at + 4]
-    extra = 0
-    while u0 & (0x80 >> extra) and extra < 7:
-        extra += 1
-    extra = max(extra - 1, 0)
-    return 5 + extra + {6: 1, 7: 2}.get(bsc, 0) + (1 if src == 12 else 2 if src in (13, 14) else 0) + 1
 
 
 def test_compare_corrupt_verbatim_sample(fa, torch):
