@@ -452,16 +452,7 @@ class FlacArray:
         dt = np.dtype(str(data.dtype).replace("torch.", "")) if isinstance(data, torch.Tensor) else data.dtype
         if dt != self._dtype:
             raise ValueError(f"data of dtype {dt} does not match the array's dtype {self._dtype}")
-        res = self._resident
-        if res is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(-1)).to(dev)  # noqa: E731
-            ft = np.float64 if self._is_int64 else np.float32
-            comp, st, nb = up(self._compressed, np.uint8), up(self._stream_starts, np.int64), up(self._stream_nbytes, np.int64)
-            off, gain = up(self._stream_offsets, ft), up(self._stream_gains, ft)
-        else:
-            dev = res["device"]
-            comp, st, nb, off, gain = res["compressed"], res["starts"], res["nbytes"], res["offsets"], res["gains"]
+        dev, comp, st, nb, off, gain = self._device_store(scale=True)
         if isinstance(data, torch.Tensor):
             x = data.to(dev).contiguous()
         else:
@@ -572,7 +563,7 @@ class FlacArray:
         cost of one decode of the whole store; explicit only (it does not follow set_encode_md5)."""
         import torch
 
-        from .libflacarray import _encode_verify_default, append_flac_device
+        from .libflacarray import append_flac_device
 
         st = self._st
         if st.global_shape != st.grid:
@@ -589,32 +580,9 @@ class FlacArray:
         n = shape[-1]
         if n == 0:
             return self.sign() if md5 else self
-        blob, s0, nb = self._splice_layout(level, "append")
-        if verify is None:
-            verify = _encode_verify_default()
-        res = self._resident
-        if res is not None:
-            dev = res["device"]
-            comp, starts, nbytes, off, gain = res["compressed"], res["starts"], res["nbytes"], res["offsets"], res["gains"]
-        else:
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a, t: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=t).reshape(-1)).to(dev)  # noqa: E731
-            ft = np.float64 if st.wide else np.float32
-            comp, starts, nbytes = up(blob, np.uint8), up(s0, np.int64), up(nb, np.int64)
-            off, gain = up(st.offsets, ft), up(st.gains, ft)
-        x = data.to(dev) if is_tensor else torch.from_numpy(np.ascontiguousarray(data)).to(dev)
-        x = x.reshape(st.count, n).contiguous()
-        # (a resident store keeps an exact-size blob, as from_device_array does; a host store only copies the bytes back)
-        comp2, starts2, nbytes2 = append_flac_device(comp, starts, nbytes, st.samples, x, level=level, offsets=off, gains=gain, verify=verify,
-                                                     compact=res is not None)
-        ishape = np.shape(st.starts)
-        new = _Store.build(tuple(st.shape[:-1]) + (st.samples + n,), None, st.dtype, comp2.cpu().numpy(),
-                           starts2.cpu().numpy().reshape(ishape), nbytes2.cpu().numpy().reshape(ishape), st.offsets, st.gains, st.dist)
-        if res is not None:
-            if res.get("index") is not None:
-                res["index"].close()
-            self._resident = dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), index=None)
-        self._st = new
+        self._splice_layout(level, "append")
+        self._splice_on_device(lambda *store, **kw: append_flac_device(*store, level=level, **kw), data, st.count,
+                               tuple(st.shape[:-1]) + (st.samples + n,), verify)
         return self.sign() if md5 else self
 
     def overwrite(self, first, data, streams=None, level=5, verify=None, md5=False):
@@ -646,7 +614,7 @@ class FlacArray:
         not keeps its header, and so a valid signature, verbatim.  `md5=True` is overwrite followed by sign()."""
         import torch
 
-        from .libflacarray import _encode_verify_default, overwrite_flac_device
+        from .libflacarray import _stream_indices, overwrite_flac_device
 
         st = self._st
         if st.global_shape != st.grid:
@@ -661,14 +629,7 @@ class FlacArray:
             if len(shape) != len(st.shape) or shape[:-1] != tuple(st.shape[:-1]):
                 raise ValueError(f"data of shape {shape} does not match the array's leading shape {tuple(st.shape[:-1])}")
         else:
-            idx = streams.detach().cpu().numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
-            if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
-                raise ValueError("streams should be a 1-D array of integer stream indices")
-            idx = idx.astype(np.int64)
-            if idx.size and (idx.min() < 0 or idx.max() >= st.count):
-                raise ValueError(f"streams holds an index outside [0, {st.count})")
-            if np.unique(idx).size != idx.size:
-                raise ValueError("streams names a stream twice")
+            idx = _stream_indices(streams, st.count)
             if len(shape) != 2 or shape[0] != idx.size:
                 raise ValueError(f"data of shape {shape} does not match the shape ({idx.size}, n) of {idx.size} streams to overwrite")
         if level < 0 or level > 8:
@@ -679,43 +640,52 @@ class FlacArray:
             raise ValueError(f"samples [{first}, {first + n}) do not lie inside streams of {st.samples} samples (append grows the store)")
         if n == 0 or (idx is not None and idx.size == 0):
             return self.sign() if md5 else self
-        blob, s0, nb = self._splice_layout(level, "overwrite")
+        self._splice_layout(level, "overwrite")
+        self._splice_on_device(lambda *store, **kw: overwrite_flac_device(*store, first, streams=idx, level=level, **kw), data,
+                               st.count if idx is None else idx.size, tuple(st.shape), verify)
+        return self.sign() if md5 else self
+
+    def _splice_on_device(self, call, data, rows, new_shape, verify):
+        """What append and overwrite do once their arguments are checked: `call(compressed, starts, nbytes, stream_size,
+        data=..., offsets=..., gains=..., verify=..., compact=...)` on the resident store or an upload, with `data` as a
+        (rows, n) tensor on that device; the result becomes the store (of shape `new_shape`) and, for a resident array, the
+        resident store, whose decode index is rebuilt on next use."""
+        import torch
+
+        from .libflacarray import _encode_verify_default
+
+        st = self._st
         if verify is None:
             verify = _encode_verify_default()
         res = self._resident
-        if res is not None:
-            dev = res["device"]
-            comp, starts, nbytes, off, gain = res["compressed"], res["starts"], res["nbytes"], res["offsets"], res["gains"]
-        else:
-            dev = torch.device("cuda", torch.cuda.current_device())
-            up = lambda a, t: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=t).reshape(-1)).to(dev)  # noqa: E731
-            ft = np.float64 if st.wide else np.float32
-            comp, starts, nbytes = up(blob, np.uint8), up(s0, np.int64), up(nb, np.int64)
-            off, gain = up(st.offsets, ft), up(st.gains, ft)
-        x = data.to(dev) if is_tensor else torch.from_numpy(np.ascontiguousarray(data)).to(dev)
-        x = x.reshape(st.count if idx is None else idx.size, n).contiguous()
-        comp2, starts2, nbytes2 = overwrite_flac_device(comp, starts, nbytes, st.samples, first, x, streams=idx, level=level, offsets=off,
-                                                        gains=gain, verify=verify, compact=res is not None)
+        dev, comp, starts, nbytes, off, gain = self._device_store(scale=True)
+        x = data.to(dev) if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+        x = x.reshape(rows, -1).contiguous()
+        # (a resident store keeps an exact-size blob, as from_device_array does; a host store only copies the bytes back)
+        comp2, starts2, nbytes2 = call(comp, starts, nbytes, st.samples, data=x, offsets=off, gains=gain, verify=verify, compact=res is not None)
         ishape = np.shape(st.starts)
-        new = _Store.build(tuple(st.shape), None, st.dtype, comp2.cpu().numpy(), starts2.cpu().numpy().reshape(ishape),
+        new = _Store.build(new_shape, None, st.dtype, comp2.cpu().numpy(), starts2.cpu().numpy().reshape(ishape),
                            nbytes2.cpu().numpy().reshape(ishape), st.offsets, st.gains, st.dist)
         if res is not None:
             if res.get("index") is not None:
                 res["index"].close()
             self._resident = dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), index=None)
         self._st = new
-        return self.sign() if md5 else self
 
-    def _device_store(self):
-        """(device, compressed, starts, nbytes) for a pass over the whole store: the resident tensors, or an upload."""
+    def _device_store(self, scale=False):
+        """(device, compressed, starts, nbytes) for a pass over the whole store: the resident tensors, or an upload.
+        `scale`: followed by the offsets and gains (None for an integer store)."""
         import torch
 
         res = self._resident
         if res is not None:
-            return res["device"], res["compressed"], res["starts"], res["nbytes"]
+            out = res["device"], res["compressed"], res["starts"], res["nbytes"]
+            return out + (res["offsets"], res["gains"]) if scale else out
         dev = torch.device("cuda", torch.cuda.current_device())
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(-1)).to(dev)  # noqa: E731
-        return dev, up(self._compressed, np.uint8), up(self._stream_starts, np.int64), up(self._stream_nbytes, np.int64)
+        up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(-1)).to(dev)  # noqa: E731
+        out = dev, up(self._compressed, np.uint8), up(self._stream_starts, np.int64), up(self._stream_nbytes, np.int64)
+        ft = np.float64 if self._is_int64 else np.float32
+        return out + (up(self._stream_offsets, ft), up(self._stream_gains, ft)) if scale else out
 
     @property
     def md5(self):

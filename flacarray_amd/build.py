@@ -16,8 +16,7 @@ DEPS = [
     os.path.join(_HERE, "csrc", "decode_kernels.hpp"),
     os.path.join(_HERE, "csrc", "quantize_kernels.hpp"),
     os.path.join(_HERE, "csrc", "std_kernels.hpp"),
-    os.path.join(_HERE, "csrc", "append_kernels.hpp"),
-    os.path.join(_HERE, "csrc", "overwrite_kernels.hpp"),
+    os.path.join(_HERE, "csrc", "splice_kernels.hpp"),
     os.path.join(_HERE, "csrc", "reduce_kernels.hpp"),
     os.path.join(os.path.dirname(_HERE), "include", "flacarray_hip.h"),
 ]

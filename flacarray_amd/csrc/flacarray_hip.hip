@@ -37,8 +37,7 @@
 #include "quantize_kernels.hpp"
 #include "verify_kernels.hpp"
 #include "std_kernels.hpp"
-#include "append_kernels.hpp"
-#include "overwrite_kernels.hpp"
+#include "splice_kernels.hpp"
 #include "md5_kernels.hpp"
 #include "reduce_kernels.hpp"
 
@@ -1603,51 +1602,201 @@ int fa_encode_i64_device(const int64_t* d_data, int64_t n_stream, int64_t stream
                              h_total_bytes, d_info, stream);
 }
 
-// ---- append (append_kernels.hpp): tail decode, encode of tail + new samples, splice -----------------------------------
-// Workspace layout (256-byte aligned regions): the (n_stream, r + n) integer image the encode reads, the decoded tails,
-// the encode's blob (its capacity), its starts | nbytes, the kept old bytes per stream, the error word and total, and
-// the encode's own workspace.
-struct AppendPlan {
-    int64_t B, r, base, nf_old, m, nf_enc, enc_cap, enc_ws;
-    size_t off_cat, off_tail, off_blob, off_idx, off_kept, off_small, off_ws, total;
+// ---- append and overwrite (splice_kernels.hpp, K10): span decode, encode of the patched span image, splice --------------
+// Both replace the frames [f0, f1) of m streams by the nf_enc frames of a fresh encode of an (m, len) integer image: the
+// old samples [lo, hi) of the span with the caller's (m, n) data laid into columns [col, col + n).  Overwrite: the image is
+// the span and the data lies inside it.  Append: the span is the old short last frame, the data lies behind it.
+// Workspace layout (256-byte aligned regions): the image the encode reads (none when the data is the whole image), the
+// decoded old span where it is narrower than the image (append), the participating streams' starts | nbytes, the encode's
+// blob (its capacity), its starts | nbytes, the row of every stream in the encode, off_old(f0) | off_old(f1) of every
+// stream, the error word and total, and the encode's own workspace.
+struct SplicePlan {
+    int64_t B, f0, f1, nf_old, nf_new, lo, hi, len, col, nf_enc, size_new, enc_cap, enc_ws;
+    bool exact;   // the caller's data is the whole image
+    bool append;  // (a negative n_old_bytes is an argument error for overwrite, a stream that does not fit for append)
+    size_t off_img, off_stage, off_sub, off_blob, off_idx, off_slot, off_off, off_small, off_ws, total;
 };
-static int make_append_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level, AppendPlan* pl) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0 || n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
-    pl->B = (level <= 2) ? 1152 : 4096;
-    pl->r = stream_size % pl->B;
-    pl->base = stream_size / pl->B;
-    pl->nf_old = (stream_size + pl->B - 1) / pl->B;
-    pl->m = pl->r + n;
-    pl->nf_enc = (pl->m + pl->B - 1) / pl->B;
-    pl->enc_cap = capacity_bytes_for(n_stream, pl->m, level, nch);
-    pl->enc_ws = single_pass_workspace_for(n_stream, pl->m, level, nch);
+// the rest of a plan whose B, f0, f1, nf_old, lo, hi, len, col and size_new are set
+static int finish_splice_plan(int nch, int64_t n_stream, int64_t m, int64_t n, uint32_t level, SplicePlan* pl) {
+    pl->nf_enc = (pl->len + pl->B - 1) / pl->B;
+    pl->nf_new = pl->f0 + pl->nf_enc + (pl->nf_old - pl->f1);
+    pl->exact = (pl->col == 0 && n == pl->len);
+    pl->enc_cap = capacity_bytes_for(m, pl->len, level, nch);
+    pl->enc_ws = single_pass_workspace_for(m, pl->len, level, nch);
     if (pl->enc_cap < 0 || pl->enc_ws < 0) return FA_ERROR_ENCODE_INIT;
+    // the frames behind the span keep their numbers: no suffix, or no change in the frame count
+    if (pl->f1 != pl->nf_old && pl->nf_enc != pl->f1 - pl->f0) return FA_ERROR_ENCODE_INIT;
     const size_t elt = 4 * (size_t)nch;
+    const bool staged = !pl->exact && pl->hi - pl->lo != pl->len;
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t o = 0;
-    pl->off_cat = o; o += (pl->r > 0) ? up((size_t)n_stream * (size_t)pl->m * elt) : 0;
-    pl->off_tail = o; o += up((size_t)n_stream * (size_t)pl->r * elt);
+    pl->off_img = o; o += pl->exact ? 0 : up((size_t)m * (size_t)pl->len * elt);
+    pl->off_stage = o; o += staged ? up((size_t)m * (size_t)(pl->hi - pl->lo) * elt) : 0;
+    pl->off_sub = o; o += up((size_t)m * 16);
     pl->off_blob = o; o += up((size_t)pl->enc_cap + 64);
-    pl->off_idx = o; o += up((size_t)n_stream * 16);
-    pl->off_kept = o; o += up((size_t)n_stream * 8);
+    pl->off_idx = o; o += up((size_t)m * 16);
+    pl->off_slot = o; o += up((size_t)n_stream * 4);
+    pl->off_off = o; o += up((size_t)n_stream * 16);
     pl->off_small = o; o += 256;
     pl->off_ws = o; o += up((size_t)pl->enc_ws);
     pl->total = o;
     return FA_ERROR_NONE;
 }
+static int make_append_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level, SplicePlan* pl) {
+    if (level > 8) return FA_ERROR_INVALID_LEVEL;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0 || n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    pl->append = true;
+    pl->B = (level <= 2) ? 1152 : 4096;
+    pl->nf_old = pl->f1 = (stream_size + pl->B - 1) / pl->B;
+    pl->f0 = stream_size / pl->B;  // the old full frames are kept
+    pl->lo = pl->f0 * pl->B;
+    pl->hi = stream_size;
+    pl->col = pl->hi - pl->lo;
+    pl->len = pl->col + n;
+    pl->size_new = stream_size + n;
+    return finish_splice_plan(nch, n_stream, n_stream, n, level, pl);
+}
+static int make_overwrite_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level, SplicePlan* pl) {
+    if (level > 8) return FA_ERROR_INVALID_LEVEL;
+    if (n_stream <= 0 || m <= 0 || m > n_stream) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0 || n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    if (first < 0 || first > stream_size || n > stream_size - first) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    pl->append = false;
+    pl->B = (level <= 2) ? 1152 : 4096;
+    pl->nf_old = (stream_size + pl->B - 1) / pl->B;
+    pl->f0 = first / pl->B;
+    pl->f1 = std::min<int64_t>(pl->nf_old, (first + n + pl->B - 1) / pl->B);
+    pl->lo = pl->f0 * pl->B;
+    pl->hi = std::min<int64_t>(pl->f1 * pl->B, stream_size);
+    pl->len = pl->hi - pl->lo;
+    pl->col = first - pl->lo;
+    pl->size_new = stream_size;
+    return finish_splice_plan(nch, n_stream, m, n, level, pl);
+}
 
 static int64_t append_workspace_for(int nch, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
-    AppendPlan pl;
+    SplicePlan pl;
     return make_append_plan(nch, n_stream, stream_size, n, level, &pl) ? -1 : (int64_t)pl.total;
 }
-// every stream grows by at most the bytes of its new encode plus 6 bytes per renumbered frame (the stream header of the
-// result is never longer than the two it replaces)
+static int64_t overwrite_workspace_for(int nch, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level) {
+    SplicePlan pl;
+    return make_overwrite_plan(nch, n_stream, stream_size, m, first, n, level, &pl) ? -1 : (int64_t)pl.total;
+}
+// a participating stream grows by at most the bytes of its span's encode plus 6 bytes per renumbered frame (the middle
+// frames it loses only make it smaller, and the stream header of the result is never longer than the two it replaces)
+static int64_t splice_capacity(const SplicePlan& pl, int64_t n_old_bytes, int64_t m) { return n_old_bytes + pl.enc_cap + 6 * pl.nf_enc * m + 64; }
 static int64_t append_capacity_for(int nch, int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level) {
-    AppendPlan pl;
-    if (make_append_plan(nch, n_stream, stream_size, n, level, &pl)) return -1;
-    return n_old_bytes + pl.enc_cap + 6 * pl.nf_enc * n_stream + 64;
+    SplicePlan pl;
+    return make_append_plan(nch, n_stream, stream_size, n, level, &pl) ? -1 : splice_capacity(pl, n_old_bytes, n_stream);
+}
+static int64_t overwrite_capacity_for(int nch, int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n,
+                                      uint32_t level) {
+    SplicePlan pl;
+    return make_overwrite_plan(nch, n_stream, stream_size, m, first, n, level, &pl) ? -1 : splice_capacity(pl, n_old_bytes, m);
+}
+
+// samples [lo, hi) of m streams into dense rows of `out`; the (m, len) image `img` into a fresh store numbered from 0
+static int decode_span(int nch, const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t m,
+                       int64_t stream_size, int64_t lo, int64_t hi, void* out, void* stream) {
+    return (nch == 2) ? fa_decode_i64_device(d_old, n_old_bytes, d_starts, d_nbytes, m, stream_size, lo, hi, reinterpret_cast<int64_t*>(out), nullptr,
+                                             nullptr, nullptr, stream, -1)
+                      : fa_decode_i32_device(d_old, n_old_bytes, d_starts, d_nbytes, m, stream_size, lo, hi, reinterpret_cast<int32_t*>(out), nullptr,
+                                             nullptr, nullptr, stream, -1);
+}
+static int encode_image(int nch, const void* img, int64_t m, int64_t len, uint32_t level, void* d_ws, int64_t ws_bytes, unsigned char* blob,
+                        int64_t cap, int64_t* e_idx, int64_t* h_total, void* stream) {
+    return (nch == 2) ? fa_encode_i64_device(reinterpret_cast<const int64_t*>(img), m, len, level, d_ws, ws_bytes, blob, cap, e_idx, e_idx + m, h_total,
+                                             nullptr, stream)
+                      : fa_encode_i32_device(reinterpret_cast<const int32_t*>(img), m, len, level, d_ws, ws_bytes, blob, cap, e_idx, e_idx + m, h_total,
+                                             nullptr, stream);
+}
+
+static int splice_run(int nch, const SplicePlan& pl, const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts,
+                      const int64_t* d_old_nbytes, int64_t n_stream, int64_t stream_size, const int64_t* d_stream_index, int64_t m, const void* d_data,
+                      int64_t n, uint32_t level, void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes,
+                      int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream) {
+    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
+    if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
+    // (the splice reads its sources in aligned 16-byte blocks)
+    if ((reinterpret_cast<uintptr_t>(d_old) & 15) || (reinterpret_cast<uintptr_t>(d_workspace) & 15) || !d_data || (!pl.append && n_old_bytes < 0))
+        return FA_ERROR_ENCODE_INIT;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* ws = reinterpret_cast<char*>(d_workspace);
+    const size_t elt = 4 * (size_t)nch;
+    // 0. the stream index, and every participating stream one this encoder wrote with the call's block size, channel count
+    //    and stream size, its seek offsets of f0 and f1 inside its body
+    SpliceArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.old = d_old; a.old_bytes = n_old_bytes; a.old_starts = d_old_starts; a.old_nbytes = d_old_nbytes;
+    a.sidx = d_stream_index;
+    a.slot = reinterpret_cast<int32_t*>(ws + pl.off_slot);
+    a.sub_starts = reinterpret_cast<int64_t*>(ws + pl.off_sub);
+    a.sub_nbytes = a.sub_starts + m;
+    a.off0 = reinterpret_cast<int64_t*>(ws + pl.off_off);
+    a.off1 = a.off0 + n_stream;
+    a.starts = d_starts; a.nbytes = d_nbytes; a.out = d_bytes;
+    a.err = reinterpret_cast<int*>(ws + pl.off_small);
+    a.n_stream = n_stream; a.m = m; a.size_old = stream_size; a.size_new = pl.size_new;
+    a.f0 = pl.f0; a.f1 = pl.f1; a.nf_old = pl.nf_old; a.nf_new = pl.nf_new;
+    a.B = (int32_t)pl.B; a.nch = nch;
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
+    if (d_stream_index) {
+        FA_HIP_TRY(hipMemsetAsync(a.slot, 0xFF, (size_t)n_stream * 4, st));
+    }
+    hipLaunchKernelGGL(splice_check_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
+    {
+        int h_err = 0;
+        FA_HIP_TRY(hipMemcpyAsync(&h_err, a.err, sizeof h_err, hipMemcpyDeviceToHost, st));
+        FA_HIP_TRY(hipStreamSynchronize(st));
+        FA_HIP_TRY(hipGetLastError());
+        if (h_err & 4) return FA_ERROR_DECODE_SEEK;
+        if (h_err) return FA_ERROR_DECODE_INIT;
+    }
+    // 1. the image: the old samples of the span, decoded (the existing decoders; through a staging copy where the image is
+    //    wider than the span), with the new samples laid into their columns -- or the new samples as they are when they are
+    //    the whole image
+    char* img = ws + pl.off_img;
+    int rc;
+    if (!pl.exact) {
+        const size_t pitch = (size_t)pl.len * elt, span = (size_t)(pl.hi - pl.lo) * elt;
+        char* dec = (span != pitch) ? ws + pl.off_stage : img;
+        rc = decode_span(nch, d_old, n_old_bytes, a.sub_starts, a.sub_nbytes, m, stream_size, pl.lo, pl.hi, dec, stream);
+        if (rc) return rc;
+        if (dec != img) {
+            FA_HIP_TRY(hipMemcpy2DAsync(img, pitch, dec, span, span, (size_t)m, hipMemcpyDeviceToDevice, st));
+        }
+        FA_HIP_TRY(hipMemcpy2DAsync(img + (size_t)pl.col * elt, pitch, d_data, (size_t)n * elt, (size_t)n * elt, (size_t)m, hipMemcpyDeviceToDevice, st));
+    } else {
+        img = reinterpret_cast<char*>(const_cast<void*>(d_data));
+    }
+    // 2. encode the image (K3F / K3G / the slot sequence, as for any array): nf_enc frames, numbered from 0
+    unsigned char* blob = reinterpret_cast<unsigned char*>(ws + pl.off_blob);
+    int64_t* e_idx = reinterpret_cast<int64_t*>(ws + pl.off_idx);
+    int64_t enc_total = 0;
+    rc = encode_image(nch, img, m, pl.len, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap, e_idx, &enc_total, stream);
+    if (rc) return rc;
+    // 3. sizes, starts (one wait: the error word and the total), then the splice
+    a.enc = blob; a.enc_bytes = enc_total; a.enc_starts = e_idx; a.enc_nbytes = e_idx + m;
+    int64_t* d_total = reinterpret_cast<int64_t*>(ws + pl.off_small + 8);
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
+    hipLaunchKernelGGL(splice_size_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_nbytes, n_stream, d_starts, d_total);
+    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
+    FA_HIP_TRY(hipMemcpyAsync(&back, a.err, sizeof back, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (back.err) return FA_ERROR_DECODE_INIT;  // (the old streams were checked above already; the new encode's index is checked here)
+    if (back.total > capacity_bytes) return FA_ERROR_ALLOC;
+    // workgroups per stream: ~64 KB of the result each (at most 1024, and a grid of fewer than 2^23 workgroups)
+    int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, back.total / n_stream / 65536));
+    while (parts > 1 && n_stream * parts >= (1LL << 23)) parts >>= 1;
+    if (n_stream * parts >= (1LL << 31) / 256) return FA_ERROR_ALLOC;
+    a.parts = (int32_t)parts;
+    hipLaunchKernelGGL(splice_kernel, dim3((unsigned)(n_stream * parts)), dim3(256), 0, st, a);
+    FA_HIP_TRY(hipGetLastError());
+    *h_total_bytes = back.total;
+    return FA_ERROR_NONE;
 }
 
 static int append_run(int nch, const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
@@ -1655,79 +1804,23 @@ static int append_run(int nch, const unsigned char* d_old, int64_t n_old_bytes, 
                       int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
                       int64_t* h_total_bytes, void* stream) {
     FA_API_LOCK;
-    AppendPlan pl;
+    SplicePlan pl;
     int rc = make_append_plan(nch, n_stream, stream_size, n, level, &pl);
     if (rc) return rc;
-    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
-    if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
-    // (the splice reads its sources in aligned 16-byte blocks)
-    if ((reinterpret_cast<uintptr_t>(d_old) & 15) || (reinterpret_cast<uintptr_t>(d_workspace) & 15) || !d_data) return FA_ERROR_ENCODE_INIT;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* ws = reinterpret_cast<char*>(d_workspace);
-    const size_t elt = 4 * (size_t)nch;
-    char* cat = ws + pl.off_cat;
-    // 0. every old stream must be one this encoder wrote with the call's block size, channel count and stream size
-    AppendArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.old = d_old; a.old_bytes = n_old_bytes; a.old_starts = d_old_starts; a.old_nbytes = d_old_nbytes;
-    a.kept = reinterpret_cast<int64_t*>(ws + pl.off_kept);
-    a.starts = d_starts; a.nbytes = d_nbytes; a.out = d_bytes; a.capacity = capacity_bytes;
-    a.err = reinterpret_cast<int*>(ws + pl.off_small);
-    a.n_stream = n_stream; a.old_size = stream_size; a.new_size = stream_size + n; a.base = pl.base; a.nf_old = pl.nf_old; a.nf_enc = pl.nf_enc;
-    a.B = (int32_t)pl.B; a.nch = nch;
-    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
-    hipLaunchKernelGGL(append_check_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
-    {
-        int h_err = 0;
-        FA_HIP_TRY(hipMemcpyAsync(&h_err, a.err, sizeof h_err, hipMemcpyDeviceToHost, st));
-        FA_HIP_TRY(hipStreamSynchronize(st));
-        FA_HIP_TRY(hipGetLastError());
-        if (h_err) return FA_ERROR_DECODE_INIT;
-    }
-    // 1. the old short last frame of every stream, decoded (the existing decoders), in front of the new samples
-    if (pl.r > 0) {
-        void* tail = ws + pl.off_tail;
-        rc = (nch == 2) ? fa_decode_i64_device(d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, pl.base * pl.B, stream_size,
-                                               reinterpret_cast<int64_t*>(tail), nullptr, nullptr, nullptr, stream, -1)
-                        : fa_decode_i32_device(d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, pl.base * pl.B, stream_size,
-                                               reinterpret_cast<int32_t*>(tail), nullptr, nullptr, nullptr, stream, -1);
-        if (rc) return rc;
-        FA_HIP_TRY(hipMemcpy2DAsync(cat, (size_t)pl.m * elt, tail, (size_t)pl.r * elt, (size_t)pl.r * elt, (size_t)n_stream, hipMemcpyDeviceToDevice, st));
-        FA_HIP_TRY(hipMemcpy2DAsync(cat + (size_t)pl.r * elt, (size_t)pl.m * elt, d_data, (size_t)n * elt, (size_t)n * elt, (size_t)n_stream,
-                                    hipMemcpyDeviceToDevice, st));
-    } else {
-        cat = reinterpret_cast<char*>(const_cast<void*>(d_data));  // (no old tail: the new samples are the encode's input as they are)
-    }
-    // 2. encode tail + new samples (K3F / K3G / the slot sequence, as for any array)
-    unsigned char* blob = reinterpret_cast<unsigned char*>(ws + pl.off_blob);
-    int64_t* e_idx = reinterpret_cast<int64_t*>(ws + pl.off_idx);
-    int64_t enc_total = 0;
-    rc = (nch == 2) ? fa_encode_i64_device(reinterpret_cast<const int64_t*>(cat), n_stream, pl.m, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap,
-                                           e_idx, e_idx + n_stream, &enc_total, nullptr, stream)
-                    : fa_encode_i32_device(reinterpret_cast<const int32_t*>(cat), n_stream, pl.m, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap,
-                                           e_idx, e_idx + n_stream, &enc_total, nullptr, stream);
+    return splice_run(nch, pl, d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, nullptr, n_stream, d_data, n, level, d_workspace,
+                      workspace_bytes, d_bytes, capacity_bytes, d_starts, d_nbytes, h_total_bytes, stream);
+}
+static int overwrite_run(int nch, const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                         int64_t n_stream, int64_t stream_size, const int64_t* d_stream_index, int64_t m, const void* d_data, int64_t first,
+                         int64_t n, uint32_t level, void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes,
+                         int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream) {
+    FA_API_LOCK;
+    if (!d_stream_index && m != n_stream) return FA_ERROR_ZERO_NSTREAM;
+    SplicePlan pl;
+    int rc = make_overwrite_plan(nch, n_stream, stream_size, m, first, n, level, &pl);
     if (rc) return rc;
-    // 3. sizes, starts (one wait: the error word and the total), then the splice
-    a.enc = blob; a.enc_bytes = enc_total; a.enc_starts = e_idx; a.enc_nbytes = e_idx + n_stream;
-    int64_t* d_total = reinterpret_cast<int64_t*>(ws + pl.off_small + 8);
-    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
-    hipLaunchKernelGGL(append_size_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_nbytes, n_stream, d_starts, d_total);
-    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
-    FA_HIP_TRY(hipMemcpyAsync(&back, a.err, sizeof back, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(hipStreamSynchronize(st));
-    FA_HIP_TRY(hipGetLastError());
-    if (back.err) return FA_ERROR_DECODE_INIT;  // (checked above already; the new encode's index is checked here)
-    if (back.total > capacity_bytes) return FA_ERROR_ALLOC;
-    // workgroups per stream: ~64 KB of the result each (at most 1024, and a grid of fewer than 2^23 workgroups)
-    int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, back.total / n_stream / 65536));
-    while (parts > 1 && n_stream * parts >= (1LL << 23)) parts >>= 1;
-    if (n_stream * parts >= (1LL << 31) / 256) return FA_ERROR_ALLOC;
-    a.parts = (int32_t)parts;
-    hipLaunchKernelGGL(append_splice_kernel, dim3((unsigned)(n_stream * parts)), dim3(256), 0, st, a);
-    FA_HIP_TRY(hipGetLastError());
-    *h_total_bytes = back.total;
-    return FA_ERROR_NONE;
+    return splice_run(nch, pl, d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, d_stream_index, m, d_data, n, level, d_workspace,
+                      workspace_bytes, d_bytes, capacity_bytes, d_starts, d_nbytes, h_total_bytes, stream);
 }
 
 }  // extern "C" (a template needs C++ linkage)
@@ -1788,152 +1881,6 @@ int fa_quantise_f32_device(const float* d_input, int64_t n_stream, int64_t n, co
 int fa_quantise_f64_device(const double* d_input, int64_t n_stream, int64_t n, const double* d_offsets, const double* d_gains, int64_t* d_output,
                            int64_t out_stride, void* stream) {
     return quantise_given_run<double, int64_t>(d_input, n_stream, n, d_offsets, d_gains, d_output, out_stride, stream);
-}
-
-// ---- overwrite (overwrite_kernels.hpp, K11): span decode, encode of the patched span, splice ---------------------------
-// Workspace layout (256-byte aligned regions): the (m, span) integer image the encode reads (none when the range is the
-// span), the participating streams' starts | nbytes, the encode's blob (its capacity), its starts | nbytes, the row of
-// every stream in the encode, off_old(f0) | off_old(f1) of every stream, the error word and total, and the encode's own
-// workspace.
-struct OverwritePlan {
-    int64_t B, nf, f0, f1, lo, hi, len, nf_enc, enc_cap, enc_ws;
-    bool exact;
-    size_t off_img, off_sub, off_blob, off_idx, off_slot, off_off, off_small, off_ws, total;
-};
-static int make_overwrite_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level, OverwritePlan* pl) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0 || m <= 0 || m > n_stream) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0 || n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
-    if (first < 0 || first > stream_size || n > stream_size - first) return FA_ERROR_DECODE_SAMPLE_RANGE;
-    pl->B = (level <= 2) ? 1152 : 4096;
-    pl->nf = (stream_size + pl->B - 1) / pl->B;
-    pl->f0 = first / pl->B;
-    pl->f1 = std::min<int64_t>(pl->nf, (first + n + pl->B - 1) / pl->B);
-    pl->lo = pl->f0 * pl->B;
-    pl->hi = std::min<int64_t>(pl->f1 * pl->B, stream_size);
-    pl->len = pl->hi - pl->lo;
-    pl->nf_enc = pl->f1 - pl->f0;
-    pl->exact = (first == pl->lo && first + n == pl->hi);
-    pl->enc_cap = capacity_bytes_for(m, pl->len, level, nch);
-    pl->enc_ws = single_pass_workspace_for(m, pl->len, level, nch);
-    if (pl->enc_cap < 0 || pl->enc_ws < 0) return FA_ERROR_ENCODE_INIT;
-    const size_t elt = 4 * (size_t)nch;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
-    pl->off_img = o; o += pl->exact ? 0 : up((size_t)m * (size_t)pl->len * elt);
-    pl->off_sub = o; o += up((size_t)m * 16);
-    pl->off_blob = o; o += up((size_t)pl->enc_cap + 64);
-    pl->off_idx = o; o += up((size_t)m * 16);
-    pl->off_slot = o; o += up((size_t)n_stream * 4);
-    pl->off_off = o; o += up((size_t)n_stream * 16);
-    pl->off_small = o; o += 256;
-    pl->off_ws = o; o += up((size_t)pl->enc_ws);
-    pl->total = o;
-    return FA_ERROR_NONE;
-}
-
-static int64_t overwrite_workspace_for(int nch, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level) {
-    OverwritePlan pl;
-    return make_overwrite_plan(nch, n_stream, stream_size, m, first, n, level, &pl) ? -1 : (int64_t)pl.total;
-}
-// a participating stream grows by at most the bytes of its span's encode plus 6 bytes per renumbered frame (the middle
-// frames it loses and the stream header of the encode only make it smaller)
-static int64_t overwrite_capacity_for(int nch, int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n,
-                                      uint32_t level) {
-    OverwritePlan pl;
-    if (make_overwrite_plan(nch, n_stream, stream_size, m, first, n, level, &pl)) return -1;
-    return n_old_bytes + pl.enc_cap + 6 * pl.nf_enc * m + 64;
-}
-
-static int overwrite_run(int nch, const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
-                         int64_t n_stream, int64_t stream_size, const int64_t* d_stream_index, int64_t m, const void* d_data, int64_t first,
-                         int64_t n, uint32_t level, void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes,
-                         int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream) {
-    FA_API_LOCK;
-    if (!d_stream_index && m != n_stream) return FA_ERROR_ZERO_NSTREAM;
-    OverwritePlan pl;
-    int rc = make_overwrite_plan(nch, n_stream, stream_size, m, first, n, level, &pl);
-    if (rc) return rc;
-    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
-    if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
-    // (the splice reads its sources in aligned 16-byte blocks)
-    if ((reinterpret_cast<uintptr_t>(d_old) & 15) || (reinterpret_cast<uintptr_t>(d_workspace) & 15) || !d_data || n_old_bytes < 0)
-        return FA_ERROR_ENCODE_INIT;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* ws = reinterpret_cast<char*>(d_workspace);
-    const size_t elt = 4 * (size_t)nch;
-    // 0. the stream index, and every participating stream one this encoder wrote with the call's block size, channel count
-    //    and stream size, its seek offsets of f0 and f1 inside its body
-    OverwriteArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.old = d_old; a.old_bytes = n_old_bytes; a.old_starts = d_old_starts; a.old_nbytes = d_old_nbytes;
-    a.sidx = d_stream_index;
-    a.slot = reinterpret_cast<int32_t*>(ws + pl.off_slot);
-    a.sub_starts = reinterpret_cast<int64_t*>(ws + pl.off_sub);
-    a.sub_nbytes = a.sub_starts + m;
-    a.off0 = reinterpret_cast<int64_t*>(ws + pl.off_off);
-    a.off1 = a.off0 + n_stream;
-    a.starts = d_starts; a.nbytes = d_nbytes; a.out = d_bytes;
-    a.err = reinterpret_cast<int*>(ws + pl.off_small);
-    a.n_stream = n_stream; a.m = m; a.size = stream_size; a.f0 = pl.f0; a.f1 = pl.f1; a.nf = pl.nf;
-    a.B = (int32_t)pl.B; a.nch = nch;
-    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
-    if (d_stream_index) {
-        FA_HIP_TRY(hipMemsetAsync(a.slot, 0xFF, (size_t)n_stream * 4, st));
-    }
-    hipLaunchKernelGGL(overwrite_check_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
-    {
-        int h_err = 0;
-        FA_HIP_TRY(hipMemcpyAsync(&h_err, a.err, sizeof h_err, hipMemcpyDeviceToHost, st));
-        FA_HIP_TRY(hipStreamSynchronize(st));
-        FA_HIP_TRY(hipGetLastError());
-        if (h_err & 4) return FA_ERROR_DECODE_SEEK;
-        if (h_err) return FA_ERROR_DECODE_INIT;
-    }
-    // 1. the image of the span: the old samples of the participating streams, decoded (the existing decoders), with the new
-    //    samples laid over their range -- or the new samples as they are when they are the whole span
-    char* img = ws + pl.off_img;
-    if (!pl.exact) {
-        rc = (nch == 2) ? fa_decode_i64_device(d_old, n_old_bytes, a.sub_starts, a.sub_nbytes, m, stream_size, pl.lo, pl.hi,
-                                               reinterpret_cast<int64_t*>(img), nullptr, nullptr, nullptr, stream, -1)
-                        : fa_decode_i32_device(d_old, n_old_bytes, a.sub_starts, a.sub_nbytes, m, stream_size, pl.lo, pl.hi,
-                                               reinterpret_cast<int32_t*>(img), nullptr, nullptr, nullptr, stream, -1);
-        if (rc) return rc;
-        FA_HIP_TRY(hipMemcpy2DAsync(img + (size_t)(first - pl.lo) * elt, (size_t)pl.len * elt, d_data, (size_t)n * elt, (size_t)n * elt, (size_t)m,
-                                    hipMemcpyDeviceToDevice, st));
-    } else {
-        img = reinterpret_cast<char*>(const_cast<void*>(d_data));
-    }
-    // 2. encode the image (K3F / K3G / the slot sequence, as for any array): frames f0 .. f1 - 1, numbered from 0
-    unsigned char* blob = reinterpret_cast<unsigned char*>(ws + pl.off_blob);
-    int64_t* e_idx = reinterpret_cast<int64_t*>(ws + pl.off_idx);
-    int64_t enc_total = 0;
-    rc = (nch == 2) ? fa_encode_i64_device(reinterpret_cast<const int64_t*>(img), m, pl.len, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap, e_idx,
-                                           e_idx + m, &enc_total, nullptr, stream)
-                    : fa_encode_i32_device(reinterpret_cast<const int32_t*>(img), m, pl.len, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap, e_idx,
-                                           e_idx + m, &enc_total, nullptr, stream);
-    if (rc) return rc;
-    // 3. sizes, starts (one wait: the error word and the total), then the splice
-    a.enc = blob; a.enc_bytes = enc_total; a.enc_starts = e_idx; a.enc_nbytes = e_idx + m;
-    int64_t* d_total = reinterpret_cast<int64_t*>(ws + pl.off_small + 8);
-    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
-    hipLaunchKernelGGL(overwrite_size_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_nbytes, n_stream, d_starts, d_total);
-    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
-    FA_HIP_TRY(hipMemcpyAsync(&back, a.err, sizeof back, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(hipStreamSynchronize(st));
-    FA_HIP_TRY(hipGetLastError());
-    if (back.err) return FA_ERROR_DECODE_INIT;
-    if (back.total > capacity_bytes) return FA_ERROR_ALLOC;
-    // workgroups per stream: ~64 KB of the result each (at most 1024, and a grid of fewer than 2^23 workgroups)
-    int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, back.total / n_stream / 65536));
-    while (parts > 1 && n_stream * parts >= (1LL << 23)) parts >>= 1;
-    if (n_stream * parts >= (1LL << 31) / 256) return FA_ERROR_ALLOC;
-    a.parts = (int32_t)parts;
-    hipLaunchKernelGGL(overwrite_splice_kernel, dim3((unsigned)(n_stream * parts)), dim3(256), 0, st, a);
-    FA_HIP_TRY(hipGetLastError());
-    *h_total_bytes = back.total;
-    return FA_ERROR_NONE;
 }
 
 int64_t fa_overwrite_workspace_bytes(int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level) {

@@ -2,6 +2,7 @@
 //
 // K1 float32_to_int32_kernel : float32_to_int32(), src/flacarray/libflacarray/utils.c:160-243
 // K2 int32_to_float32_kernel : int32_to_float32(), src/flacarray/libflacarray/utils.c:350-368
+//    quantise_rows_kernel    : the same quantisation with GIVEN offsets and gains (append / overwrite on a float store)
 //
 // The arithmetic follows the reference operation by operation: float subtract and float
 // multiply, then a DOUBLE add of +-0.5 and truncation (utils.c:232-240); offset snapped to a
@@ -305,6 +306,33 @@ FA_GLOBAL __global__ __launch_bounds__(256) void int64_to_float64_kernel(const i
     const int64_t* in = input + is * stream_size;
     double* out = output + is * stream_size;
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) out[i] = off + coeff * (double)in[i];  // :343
+}
+
+// ---- quantise_rows_kernel: float32 / float64 samples quantised with GIVEN per-stream offsets and gains (utils.c:229-240,
+// :316-323: the arithmetic of quantise_f32 / quantise_f64), written at a row stride of the caller's choice.  What append and
+// overwrite quantise the new samples of a float store with.
+template <typename F, typename I>
+__device__ __forceinline__ I quantise_given(F x, F off, F gain);
+template <>
+__device__ __forceinline__ int32_t quantise_given<float, int32_t>(float x, float off, float gain) { return quantise_f32(x, off, gain); }
+template <>
+__device__ __forceinline__ int64_t quantise_given<double, int64_t>(double x, double off, double gain) { return quantise_f64(x, off, gain); }
+
+// grid-stride over n_stream * n samples; out[s * out_stride + i] (a row stride > n writes into a wider image)
+template <typename F, typename I>
+__global__ __launch_bounds__(256) void quantise_rows_kernel(const F* __restrict__ in, int64_t n_stream, int64_t n, const F* __restrict__ offsets,
+                                                            const F* __restrict__ gains, I* __restrict__ out, int64_t out_stride,
+                                                            int* __restrict__ flags) {
+    const int64_t total = n_stream * n;
+    bool nan = false;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int64_t s = g / n;
+        const int64_t i = g - s * n;
+        const F x = in[g];
+        nan = nan || (x != x);
+        out[s * out_stride + i] = quantise_given<F, I>(x, offsets[s], gains[s]);
+    }
+    if (nan) atomicOr(flags, 1);
 }
 
 }  // namespace fa

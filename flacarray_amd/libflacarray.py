@@ -1210,6 +1210,22 @@ def decode_slices_device(compressed, starts, nbytes, stream_size, slice_stream, 
     return out, out_off
 
 
+def _stream_indices(streams, n_stream):
+    """`streams` (None, or a 1-D integer array or tensor of flat C-order stream indices) as an int64 numpy array or None;
+    an index out of range or named twice raises ValueError."""
+    if streams is None:
+        return None
+    idx = streams.detach().cpu().numpy() if isinstance(streams, _torch().Tensor) else np.asarray(streams)
+    if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+        raise ValueError("streams should be a 1-D array of integer stream indices")
+    idx = idx.astype(np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= n_stream):
+        raise ValueError(f"streams holds an index outside [0, {n_stream})")
+    if np.unique(idx).size != idx.size:
+        raise ValueError("streams names a stream twice")
+    return idx
+
+
 def _reduce_args(n_stream, stream_size, width, first_sample, last_sample, streams):
     """The argument checks of the binned reduction (ValueError, before anything touches the GPU).  Returns (first, last,
     width, nbins, stream indices as an int64 numpy array or None)."""
@@ -1227,18 +1243,7 @@ def _reduce_args(n_stream, stream_size, width, first_sample, last_sample, stream
     if width < 1:
         raise ValueError("width should be at least one sample")
     width = min(width, n)
-    idx = None
-    if streams is not None:
-        torch = _torch()
-        idx = streams.detach().cpu().numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
-        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
-            raise ValueError("streams should be a 1-D array of integer stream indices")
-        idx = idx.astype(np.int64)
-        if idx.size and (idx.min() < 0 or idx.max() >= n_stream):
-            raise ValueError(f"streams holds an index outside [0, {n_stream})")
-        if np.unique(idx).size != idx.size:
-            raise ValueError("streams names a stream twice")
-    return first, last, width, -(-n // width), idx
+    return first, last, width, -(-n // width), _stream_indices(streams, n_stream)
 
 
 def _reduce_outputs(rows, nbins, wide, dev):
@@ -1513,6 +1518,114 @@ def float64_to_int64_device(data, quanta=None):
     return out, offsets.reshape(lead), gains.reshape(lead)
 
 
+def _splice_checks(compressed, starts, nbytes, level, data, offsets, gains, streams=None):
+    """The argument checks append and overwrite share (ValueError).  Returns (n_stream, n, stream indices as an int64
+    numpy array or None)."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64 or starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes should be int64 tensors of one shape")
+    if level < 0 or level > 8:
+        raise ValueError("FLAC only supports compression levels 0-8")
+    n_stream = int(np.prod(starts.shape))
+    if data.dim() == 0:
+        raise ValueError("data needs a stream axis")
+    n = int(data.shape[-1])
+    idx = _stream_indices(streams, n_stream)
+    if idx is None:
+        if tuple(data.shape) not in ((n_stream, n), tuple(starts.shape) + (n,)) and not (data.dim() == 1 and n_stream == 1):
+            raise ValueError(f"data of shape {tuple(data.shape)} does not match {n_stream} streams (starts of shape {tuple(starts.shape)})")
+    elif tuple(data.shape) != (idx.size, n):
+        raise ValueError(f"data of shape {tuple(data.shape)} does not match {idx.size} streams to overwrite")
+    is_float = data.dtype in (torch.float32, torch.float64)
+    if data.dtype not in (torch.int32, torch.int64) and not is_float:
+        raise ValueError(f"Unsupported data type '{data.dtype}': int32, int64, float32 or float64")
+    if is_float != (offsets is not None) or (offsets is None) != (gains is None):
+        raise ValueError("float data need the store's offsets and gains, integer data take neither")
+    return n_stream, n, idx
+
+
+def _splice_flac_device(op, compressed, starts, nbytes, stream_size, data, idx, first, level, offsets, gains, verify, compact):
+    """What append and overwrite do on the device: quantise float `data` with the store's offsets and gains, run
+    fa_<op>_i32_device / fa_<op>_i64_device into fresh buffers, and (verify) decode the re-encoded span from the result and
+    compare it with the old span patched by `data`.  `idx`: the streams that take part (None: all); `first`: the sample
+    the data starts at (append: stream_size).  Returns (compressed, starts, nbytes) of the new store."""
+    torch = _torch()
+    word = {"append": "Appending", "overwrite": "Overwriting"}[op]
+    dev = compressed.device
+    n_stream = int(np.prod(starts.shape))
+    n = int(data.shape[-1])
+    m = n_stream if idx is None else int(idx.size)
+    wide = data.dtype in (torch.int64, torch.float64)
+    L = _lib.lib()
+    data = data.reshape(m, n).contiguous()
+    with _on_device(dev):
+        d_idx = None if idx is None else torch.from_numpy(idx).to(dev)
+        if data.dtype in (torch.float32, torch.float64):
+            off = offsets.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+            gain = gains.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
+            if off.numel() != n_stream or gain.numel() != n_stream:
+                raise ValueError("offsets and gains need one value per stream")
+            if d_idx is not None:
+                off, gain = off[d_idx].contiguous(), gain[d_idx].contiguous()
+            ints = torch.empty((m, n), dtype=torch.int64 if wide else torch.int32, device=dev)
+            errcode = (L.fa_quantise_f64_device if wide else L.fa_quantise_f32_device)(
+                _dp(data), m, n, _dp(off), _dp(gain), _dp(ints), n, _stream_ptr())
+            if errcode & _lib.ERROR_NAN_INPUT:
+                raise RuntimeError("Cannot convert data with NaNs to integers")
+            if errcode != 0:
+                raise RuntimeError(f"Quantisation failed, return code = {errcode}")
+            data = ints
+        comp = compressed.contiguous()
+        st, nb = starts.reshape(-1).contiguous(), nbytes.reshape(-1).contiguous()
+        # (the C signatures differ in the geometry only: append takes n, overwrite the stream index, m, first and n)
+        geom = (n,) if op == "append" else (m, first, n)
+        where = (_dp(data), n) if op == "append" else (_dp(d_idx), m, _dp(data), first, n)
+        sfx = "_i64" if wide else ""
+        ws_bytes = getattr(L, f"fa_{op}_workspace_bytes{sfx}")(n_stream, stream_size, *geom, level)
+        cap = getattr(L, f"fa_{op}_capacity_bytes{sfx}")(comp.numel(), n_stream, stream_size, *geom, level)
+        if ws_bytes < 0 or cap < 0:
+            raise RuntimeError(f"{word} failed: invalid geometry")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        buf = torch.empty(cap, dtype=torch.uint8, device=dev)
+        index = torch.empty(2 * n_stream, dtype=torch.int64, device=dev)
+        total = ctypes.c_int64(0)
+        errcode = getattr(L, f"fa_{op}_{'i64' if wide else 'i32'}_device")(
+            _dp(comp), comp.numel(), _dp(st), _dp(nb), n_stream, stream_size, *where, level, _dp(ws), ws_bytes, _dp(buf), cap,
+            _dp(index[:n_stream]), _dp(index[n_stream:]), ctypes.byref(total), _stream_ptr())
+    if errcode == 8192:  # FA_ERROR_DECODE_INIT
+        raise ValueError(f"{word} needs streams written by this library (a SEEKTABLE with one point per frame) with the block size of "
+                         f"level {level}, {2 if wide else 1} channel(s) ({data.dtype} data) and {stream_size} samples")
+    if errcode != 0:
+        raise RuntimeError(f"{word} failed, return code = {errcode}")
+    blob = buf[: total.value]
+    if compact:
+        blob = blob.clone()
+        del buf
+    out = (blob, index[:n_stream].reshape(starts.shape), index[n_stream:].reshape(starts.shape))
+    if verify:
+        # the re-encoded span: [lo, hi_old) of the old streams, [lo, hi_new) of the new ones
+        B = 1152 if level <= 2 else 4096
+        size_new = max(stream_size, first + n)
+        lo = first // B * B
+        hi_old, hi_new = (min(-(-(first + n) // B) * B, size) for size in (stream_size, size_new))
+        rows = slice(None) if d_idx is None else d_idx
+        span = decode_flac_device(out[0], index[:n_stream][rows], index[n_stream:][rows], size_new, lo, hi_new, is_int64=wide,
+                                  verify=True).reshape(m, -1)
+        if lo == first and hi_new == first + n:
+            want = data
+        else:
+            old = decode_flac_device(comp, st[rows], nb[rows], stream_size, lo, hi_old, is_int64=wide).reshape(m, -1)
+            want = torch.cat([old, old.new_empty((m, hi_new - hi_old))], dim=1)
+            want[:, first - lo : first - lo + n] = data
+        bad = (span != want).any(dim=1)
+        if bool(bad.any()):
+            at = torch.where(bad, (span != want).int().argmax(dim=1) + lo, torch.full_like(bad, -1, dtype=torch.int64))
+            _raise_on_mismatch(at)
+    return out
+
+
 def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, offsets=None, gains=None, verify=False, compact=False,
                        md5=False):
     """Extend every stream of a device-resident store by data.shape[-1] samples: returns the new (compressed, starts,
@@ -1534,82 +1647,15 @@ def append_flac_device(compressed, starts, nbytes, stream_size, data, level=5, o
     The splice writes a fresh stream header, so the result is UNSIGNED (MD5 field zero) whatever the old store was: a
     finished digest cannot be resumed.  `md5=True` signs it, at the cost of one decode of the whole new store
     (check_md5_device's chunked pass); explicit only -- it does not follow set_encode_md5."""
-    torch = _torch()
-    if compressed.dtype != torch.uint8:
-        raise ValueError("Compressed data should be of type uint8")
-    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64 or starts.shape != nbytes.shape:
-        raise ValueError("starts and nbytes should be int64 tensors of one shape")
-    if level < 0 or level > 8:
-        raise ValueError("FLAC only supports compression levels 0-8")
-    n_stream = int(np.prod(starts.shape))
-    if data.dim() == 0:
-        raise ValueError("data needs a stream axis")
-    n = int(data.shape[-1])
-    if tuple(data.shape) not in ((n_stream, n), tuple(starts.shape) + (n,)) and not (data.dim() == 1 and n_stream == 1):
-        raise ValueError(f"data of shape {tuple(data.shape)} does not match {n_stream} streams (starts of shape {tuple(starts.shape)})")
-    is_float = data.dtype in (torch.float32, torch.float64)
-    if data.dtype not in (torch.int32, torch.int64) and not is_float:
-        raise ValueError(f"Unsupported data type '{data.dtype}': int32, int64, float32 or float64")
-    if is_float != (offsets is not None) or (offsets is None) != (gains is None):
-        raise ValueError("float data need the store's offsets and gains, integer data take neither")
+    n_stream, n, _ = _splice_checks(compressed, starts, nbytes, level, data, offsets, gains)
     dev = compressed.device
     if not (compressed.is_cuda and data.device == dev and starts.device == dev and nbytes.device == dev):
         raise RuntimeError("append_flac_device needs compressed, starts, nbytes and data on the same GPU")
     if n == 0:
         return compressed, starts, nbytes
-    wide = data.dtype in (torch.int64, torch.float64)
-    L = _lib.lib()
-    data = data.reshape(n_stream, n).contiguous()
-    with _on_device(dev):
-        if is_float:
-            off = offsets.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
-            gain = gains.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
-            if off.numel() != n_stream or gain.numel() != n_stream:
-                raise ValueError("offsets and gains need one value per stream")
-            ints = torch.empty((n_stream, n), dtype=torch.int64 if wide else torch.int32, device=dev)
-            errcode = (L.fa_quantise_f64_device if wide else L.fa_quantise_f32_device)(
-                _dp(data), n_stream, n, _dp(off), _dp(gain), _dp(ints), n, _stream_ptr())
-            if errcode & _lib.ERROR_NAN_INPUT:
-                raise RuntimeError("Cannot convert data with NaNs to integers")
-            if errcode != 0:
-                raise RuntimeError(f"Quantisation failed, return code = {errcode}")
-            data = ints
-        comp = compressed.contiguous()
-        st, nb = starts.reshape(-1).contiguous(), nbytes.reshape(-1).contiguous()
-        ws_bytes = (L.fa_append_workspace_bytes_i64 if wide else L.fa_append_workspace_bytes)(n_stream, stream_size, n, level)
-        cap = (L.fa_append_capacity_bytes_i64 if wide else L.fa_append_capacity_bytes)(comp.numel(), n_stream, stream_size, n, level)
-        if ws_bytes < 0 or cap < 0:
-            raise RuntimeError("Appending failed: invalid geometry")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        buf = torch.empty(cap, dtype=torch.uint8, device=dev)
-        index = torch.empty(2 * n_stream, dtype=torch.int64, device=dev)
-        total = ctypes.c_int64(0)
-        errcode = (L.fa_append_i64_device if wide else L.fa_append_i32_device)(
-            _dp(comp), comp.numel(), _dp(st), _dp(nb), n_stream, stream_size, _dp(data), n, level, _dp(ws), ws_bytes, _dp(buf), cap,
-            _dp(index[:n_stream]), _dp(index[n_stream:]), ctypes.byref(total), _stream_ptr())
-    if errcode == 8192:  # FA_ERROR_DECODE_INIT
-        raise ValueError("Appending needs streams written by this library (a SEEKTABLE with one point per frame) with the block size of "
-                         f"level {level}, {2 if wide else 1} channel(s) ({data.dtype} data) and {stream_size} samples")
-    if errcode != 0:
-        raise RuntimeError(f"Appending failed, return code = {errcode}")
-    blob = buf[: total.value]
-    if compact:
-        blob = blob.clone()
-        del buf
-    out = (blob, index[:n_stream].reshape(starts.shape), index[n_stream:].reshape(starts.shape))
-    if verify:
-        B = 1152 if level <= 2 else 4096
-        lo = stream_size - stream_size % B
-        span = decode_flac_device(out[0], out[1], out[2], stream_size + n, lo, stream_size + n, is_int64=wide, verify=True).reshape(n_stream, -1)
-        want = data
-        if lo < stream_size:
-            old = decode_flac_device(comp, st, nb, stream_size, lo, stream_size, is_int64=wide).reshape(n_stream, -1)
-            want = torch.cat([old, data], dim=1)
-        bad = (span != want).any(dim=1)
-        if bool(bad.any()):
-            first = torch.where(bad, (span != want).int().argmax(dim=1) + lo, torch.full_like(bad, -1, dtype=torch.int64))
-            _raise_on_mismatch(first)
+    out = _splice_flac_device("append", compressed, starts, nbytes, stream_size, data, None, stream_size, level, offsets, gains, verify, compact)
     if md5:
+        wide = data.dtype in (_torch().int64, _torch().float64)
         _, digests = check_md5_device(out[0], out[1], out[2], stream_size + n, is_int64=wide, return_digests=True)
         sign_streams_device(out[0], out[1], digests)
     return out
@@ -1638,104 +1684,13 @@ def overwrite_flac_device(compressed, starts, nbytes, stream_size, first, data, 
     channel count or stream size than the call's raises ValueError before anything is decoded.  `verify=True`: decode the
     re-encoded span of the participating streams from the result and compare it with the patched old span; a difference
     raises RuntimeError."""
-    torch = _torch()
-    if compressed.dtype != torch.uint8:
-        raise ValueError("Compressed data should be of type uint8")
-    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64 or starts.shape != nbytes.shape:
-        raise ValueError("starts and nbytes should be int64 tensors of one shape")
-    if level < 0 or level > 8:
-        raise ValueError("FLAC only supports compression levels 0-8")
-    n_stream = int(np.prod(starts.shape))
-    if data.dim() == 0:
-        raise ValueError("data needs a stream axis")
-    n = int(data.shape[-1])
-    idx = None
-    if streams is None:
-        m = n_stream
-        if tuple(data.shape) not in ((n_stream, n), tuple(starts.shape) + (n,)) and not (data.dim() == 1 and n_stream == 1):
-            raise ValueError(f"data of shape {tuple(data.shape)} does not match {n_stream} streams (starts of shape {tuple(starts.shape)})")
-    else:
-        idx = streams.detach().cpu().numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
-        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
-            raise ValueError("streams should be a 1-D array of integer stream indices")
-        idx = idx.astype(np.int64)
-        m = int(idx.size)
-        if m and (idx.min() < 0 or idx.max() >= n_stream):
-            raise ValueError(f"streams holds an index outside [0, {n_stream})")
-        if np.unique(idx).size != m:
-            raise ValueError("streams names a stream twice")
-        if tuple(data.shape) != (m, n):
-            raise ValueError(f"data of shape {tuple(data.shape)} does not match {m} streams to overwrite")
-    is_float = data.dtype in (torch.float32, torch.float64)
-    if data.dtype not in (torch.int32, torch.int64) and not is_float:
-        raise ValueError(f"Unsupported data type '{data.dtype}': int32, int64, float32 or float64")
-    if is_float != (offsets is not None) or (offsets is None) != (gains is None):
-        raise ValueError("float data need the store's offsets and gains, integer data take neither")
+    n_stream, n, idx = _splice_checks(compressed, starts, nbytes, level, data, offsets, gains, streams)
     first = int(first)
     if first < 0 or first + n > stream_size:
         raise ValueError(f"samples [{first}, {first + n}) do not lie inside streams of {stream_size} samples")
     dev = compressed.device
     if not (compressed.is_cuda and data.device == dev and starts.device == dev and nbytes.device == dev):
         raise RuntimeError("overwrite_flac_device needs compressed, starts, nbytes and data on the same GPU")
-    if n == 0 or m == 0:
+    if n == 0 or (idx is not None and idx.size == 0):
         return compressed, starts, nbytes
-    wide = data.dtype in (torch.int64, torch.float64)
-    L = _lib.lib()
-    data = data.reshape(m, n).contiguous()
-    with _on_device(dev):
-        d_idx = None if idx is None else torch.from_numpy(idx).to(dev)
-        if is_float:
-            off = offsets.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
-            gain = gains.to(device=dev, dtype=data.dtype).reshape(-1).contiguous()
-            if off.numel() != n_stream or gain.numel() != n_stream:
-                raise ValueError("offsets and gains need one value per stream")
-            if d_idx is not None:
-                off, gain = off[d_idx].contiguous(), gain[d_idx].contiguous()
-            ints = torch.empty((m, n), dtype=torch.int64 if wide else torch.int32, device=dev)
-            errcode = (L.fa_quantise_f64_device if wide else L.fa_quantise_f32_device)(
-                _dp(data), m, n, _dp(off), _dp(gain), _dp(ints), n, _stream_ptr())
-            if errcode & _lib.ERROR_NAN_INPUT:
-                raise RuntimeError("Cannot convert data with NaNs to integers")
-            if errcode != 0:
-                raise RuntimeError(f"Quantisation failed, return code = {errcode}")
-            data = ints
-        comp = compressed.contiguous()
-        st, nb = starts.reshape(-1).contiguous(), nbytes.reshape(-1).contiguous()
-        ws_bytes = (L.fa_overwrite_workspace_bytes_i64 if wide else L.fa_overwrite_workspace_bytes)(n_stream, stream_size, m, first, n, level)
-        cap = (L.fa_overwrite_capacity_bytes_i64 if wide else L.fa_overwrite_capacity_bytes)(comp.numel(), n_stream, stream_size, m, first, n, level)
-        if ws_bytes < 0 or cap < 0:
-            raise RuntimeError("Overwriting failed: invalid geometry")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        buf = torch.empty(cap, dtype=torch.uint8, device=dev)
-        index = torch.empty(2 * n_stream, dtype=torch.int64, device=dev)
-        total = ctypes.c_int64(0)
-        errcode = (L.fa_overwrite_i64_device if wide else L.fa_overwrite_i32_device)(
-            _dp(comp), comp.numel(), _dp(st), _dp(nb), n_stream, stream_size, _dp(d_idx), m, _dp(data), first, n, level, _dp(ws), ws_bytes,
-            _dp(buf), cap, _dp(index[:n_stream]), _dp(index[n_stream:]), ctypes.byref(total), _stream_ptr())
-    if errcode == 8192:  # FA_ERROR_DECODE_INIT
-        raise ValueError("Overwriting needs streams written by this library (a SEEKTABLE with one point per frame) with the block size of "
-                         f"level {level}, {2 if wide else 1} channel(s) ({data.dtype} data) and {stream_size} samples")
-    if errcode != 0:
-        raise RuntimeError(f"Overwriting failed, return code = {errcode}")
-    blob = buf[: total.value]
-    if compact:
-        blob = blob.clone()
-        del buf
-    out = (blob, index[:n_stream].reshape(starts.shape), index[n_stream:].reshape(starts.shape))
-    if verify:
-        B = 1152 if level <= 2 else 4096
-        lo = first // B * B
-        hi = min(-(-(first + n) // B) * B, stream_size)
-        rows = slice(None) if d_idx is None else d_idx
-        span = decode_flac_device(out[0], index[:n_stream][rows], index[n_stream:][rows], stream_size, lo, hi, is_int64=wide,
-                                  verify=True).reshape(m, -1)
-        if lo == first and hi == first + n:
-            want = data
-        else:
-            want = decode_flac_device(comp, st[rows], nb[rows], stream_size, lo, hi, is_int64=wide).reshape(m, -1).clone()
-            want[:, first - lo : first - lo + n] = data
-        bad = (span != want).any(dim=1)
-        if bool(bad.any()):
-            at = torch.where(bad, (span != want).int().argmax(dim=1) + lo, torch.full_like(bad, -1, dtype=torch.int64))
-            _raise_on_mismatch(at)
-    return out
+    return _splice_flac_device("overwrite", compressed, starts, nbytes, stream_size, data, idx, first, level, offsets, gains, verify, compact)

@@ -186,7 +186,8 @@ int fa_encode_i64_device(const int64_t* d_data, int64_t n_stream, int64_t stream
  * n samples -- d_data[n_stream][n], int32 for one-channel streams (fa_append_i32_device), int64 for two-channel streams
  * (fa_append_i64_device) -- so that the result is, byte for byte, what fa_encode_i32_device / fa_encode_i64_device writes for
  * the concatenation (same level: its block size must be the one in the streams' STREAMINFO).  The old short last frame of
- * every stream is decoded, the (n_stream, r + n) image of it and the new samples is encoded, and one splice kernel writes the
+ * every stream is decoded, the (n_stream, r + n) image of it and the new samples is encoded, and one splice kernel (the one
+ * fa_overwrite_*_device runs: the span is the old short last frame, nothing lies behind it and the stream grows) writes the
  * result: a new stream header, the kept old frames verbatim, the new frames renumbered (UTF-8 frame number, CRC-8 and --
  * through the linear CRC identity, without a pass over the payload -- CRC-16).  d_old is 16-byte aligned and unchanged; the
  * caller owns it, d_data, the workspace (fa_append_workspace_bytes[_i64]: the integer image, the encode's blob and its own

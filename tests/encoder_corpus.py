@@ -1,7 +1,7 @@
 """Encoder decision corpus: named, seeded inputs that drive every rare branch of the encoder specification
 (oracle/flac_oracle.c, rice_search through encode_frame) -- and so of the HIP encoder bodies that restate it: K3F
 (csrc/encode_fused.hpp), the slot body shared by K3G and the slot sequence (csrc/encode_kernels.hpp) and the append
-re-encode (csrc/append_kernels.hpp).  Nothing here calls the library: tests/test_encoder_corpus.py audits, on the
+re-encode (csrc/splice_kernels.hpp).  Nothing here calls the library: tests/test_encoder_corpus.py audits, on the
 oracle's decision trace, that every decision of its table is reached by a case that lists it, and
 tests/test_gpu_encoder_corpus.py runs every case through every route that takes its geometry.
 

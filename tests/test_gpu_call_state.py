@@ -267,7 +267,8 @@ def test_c_slot_sequence_on_poisoned_buffers(torch, oracle, L, name, poison):
 def test_splice_workspace_poisoned(fa, torch, oracle, L, wide, op, poison):
     """fa_append_*_device / fa_overwrite_*_device take a caller's workspace too (the Python layer hands them a fresh
     torch.empty): poisoned, with the output full of 0xA5 and a guard behind its capacity, the result is the oracle's encode
-    of the concatenated / patched samples."""
+    of the concatenated / patched samples.  The workspace is exactly the bytes the query asks for, with a guard of its own
+    behind them that the call must leave as it is."""
     ns, n, m, first, level = 6, 9000, 5000, 3000, 5
     gen = _i64 if wide else sinusoid_noise_i32
     x, new = gen(ns, n, seed=301), gen(ns if op != "overwrite_streams" else 2, m, seed=302)
@@ -286,7 +287,8 @@ def test_splice_workspace_poisoned(fa, torch, oracle, L, wide, op, poison):
         expect = x.copy()
         expect[slice(None) if idx is None else idx, first : first + m] = new
     assert need > 0 and cap > 0
-    ws = torch.full((need,), {"zeros": 0x00, "ones": 0xFF, "a5": 0xA5}[poison], dtype=torch.uint8, device="cuda")
+    ws = torch.full((need + 4096,), {"zeros": 0x00, "ones": 0xFF, "a5": 0xA5}[poison], dtype=torch.uint8, device="cuda")
+    ws[need:] = 0x3C
     buf = torch.full((cap + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
     d_st = torch.full((ns,), -1, dtype=torch.int64, device="cuda")
     d_nb = torch.full((ns,), -1, dtype=torch.int64, device="cuda")
@@ -303,6 +305,7 @@ def test_splice_workspace_poisoned(fa, torch, oracle, L, wide, op, poison):
             _vp(d_st), _vp(d_nb), ctypes.byref(total), None)
     torch.cuda.synchronize()
     assert rc == 0
+    assert bool((ws[need:] == 0x3C).all()), "bytes behind workspace_bytes were written"
     blob_o, st_o, nb_o = (oracle.encode_i64 if wide else oracle.encode_i32)(expect, level)
     assert total.value == blob_o.size
     assert np.array_equal(buf[: total.value].cpu().numpy(), blob_o)

@@ -4,8 +4,9 @@ appends of 2^16 and 2^20 samples per stream, the three pieces timed separately w
   encode        encode_flac_device of the (n_stream, r + n) image
   append        append_flac_device, all of it (tail decode + copies + encode + sizes + the splice)
 -- so that splice + host waits ~ append - tail decode - encode; the splice kernel alone is what a
-`rocprofv3 --kernel-trace --stats` run of this tool reports for append_splice_kernel.  --tail R makes the store N = 2^20 + R
-samples long (R > 0: a short last frame).  The median and minimum of --reps runs are printed as one JSON line per case.
+`rocprofv3 --kernel-trace --stats` run of this tool reports for splice_kernel (the one kernel append and overwrite
+share).  --tail R makes the store N = 2^20 + R samples long (R > 0: a short last frame).  The median and minimum of
+--reps runs are printed as one JSON line per case.
 Results: profiles/append.md.  Usage: python -m tools.bench_append [--reps N] [--streams S] [--tail R]
 """
 import argparse

@@ -5,10 +5,11 @@ streams and for 64 of them, the pieces timed separately with device events --
   encode        encode_flac_device of the (m, span) image
   overwrite     overwrite_flac_device, all of it (check + span decode + copy + encode + sizes + the splice)
 -- so that splice + host waits ~ overwrite - span decode - encode; the splice kernel alone is what a
-`rocprofv3 --kernel-trace --stats` run of this tool reports for overwrite_splice_kernel.  Two baselines on the same store
-in the same run: append_flac_device of the same n (all streams), and what a user must do without overwrite: decode the
-whole array and encode_flac_device all of it (--no-full skips it).  The median and minimum of --reps runs after a
-warm-up round are printed as one JSON line per case.  Results: profiles/overwrite.md.
+`rocprofv3 --kernel-trace --stats` run of this tool reports for splice_kernel (the one kernel append and overwrite
+share).  Two baselines on the same store in the same run: append_flac_device of the same n (all streams), and what a
+user must do without overwrite: decode the whole array and encode_flac_device all of it (--no-full skips it).  The
+median and minimum of --reps runs after a warm-up round are printed as one JSON line per case.  Results:
+profiles/overwrite.md.
 Usage: python -m tools.bench_overwrite [--reps N] [--streams S] [--subset M] [--no-full]
 """
 import argparse
