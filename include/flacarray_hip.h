@@ -260,7 +260,10 @@ int fa_quantise_f64_device(const double* d_input, int64_t n_stream, int64_t n, c
 /* Decode [first_sample,last_sample) (or everything when either is negative) of n_stream
  * streams.  Exactly one of d_out_i32 / d_out_f32 is non-NULL; with d_out_f32 the int32 ->
  * float32 restore (utils.c:350-368) is fused into the store and d_offsets/d_gains[n_stream]
- * are required.  verify: see fa_set_decode_verify.  Returns the OR of the error bits (synchronises the stream). */
+ * are required.  verify: see fa_set_decode_verify.  Returns the OR of the error bits (synchronises the stream).
+ * Every decode entry point (this one, its two-channel twin, the slice calls and fa_decode_indexed) needs the output
+ * pointer aligned to its element type only, takes arbitrary out_offset values as long as the slices' output ranges do
+ * not overlap, and writes nothing outside the requested elements (tests/test_gpu_decode_footprint.py). */
 int fa_decode_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts,
                          const int64_t* d_nbytes, int64_t n_stream, int64_t stream_size, int64_t first_sample,
                          int64_t last_sample, int32_t* d_out_i32, float* d_out_f32, const float* d_offsets,
