@@ -456,13 +456,15 @@ bool run_verify_beside_begin(hipStream_t st) {
     return hipStreamWaitEvent(ds->verify_stream, ds->verify_ev[0], 0) == hipSuccess;
 }
 // (called after K7 has been queued on `st`: K7's workgroups take the chip first, K9's fill what they leave)
-void run_verify_beside_launch(const DecodeArgs& a, hipStream_t st) {
+// Returns whether K9 was queued: false means that nothing has been checked, and the caller checks after K7 as before.
+bool run_verify_beside_launch(const DecodeArgs& a, hipStream_t st) {
     DeviceState* ds = dev_state();
     const uint16_t* tab = nullptr;
-    if (!ds || !ds->verify_stream || get_crc_tab_fused(&tab)) return;
+    if (!ds || !ds->verify_stream || get_crc_tab_fused(&tab)) return false;
     hipLaunchKernelGGL(verify_crc16_kernel, dim3((unsigned)((a.n_tasks + 3) / 4)), dim3(256), 0, ds->verify_stream, a, tab);
     (void)hipEventRecord(ds->verify_ev[1], ds->verify_stream);
     (void)hipStreamWaitEvent(st, ds->verify_ev[1], 0);
+    return true;
 }
 
 constexpr size_t kPinBytes = 512u << 10;  // samples (larger results go by DMA: 1.6 MB took 307 us this way, 298 by copy); 64 bytes of status words follow
@@ -904,10 +906,8 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     prof_end(2, st);
-    if (beside) {
-        run_verify_beside_launch(a, st);
-        verify = 0;  // (done: the check at the end of this function is not repeated)
-    }
+    // (queued: the check at the end of this function is not repeated; not queued: it runs there, after K7)
+    if (beside && run_verify_beside_launch(a, st)) verify = 0;
     prof_end(4, st);  // (deeper-history passes, when a stream needs them, follow outside this pair)
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));

@@ -1079,9 +1079,9 @@ def check_md5_device(compressed, starts, nbytes, stream_size, is_int64=False, re
     return (status, digests.reshape(tuple(starts.shape) + (16,))) if return_digests else status
 
 
-def _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, is_int64):
+def _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, is_int64, verify):
     """A failed decode call whose streams differ in block size: one launch per block size (see _blocksize_classes),
-    rows scattered back into `out`.  Anything else raises the reference's error."""
+    rows scattered back into `out`, each launch with the caller's `verify`.  Anything else raises the reference's error."""
     torch = _torch()
     st, nb = starts.reshape(-1), nbytes.reshape(-1)
     n_stream = st.numel()
@@ -1096,7 +1096,7 @@ def _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first
         out2[gi] = decode_flac_device(
             compressed, st[gi].contiguous(), nb[gi].contiguous(), stream_size, first_sample, last_sample,
             offsets=None if offsets is None else offsets.reshape(-1)[gi.to(offsets.device)],
-            gains=None if gains is None else gains.reshape(-1)[gi.to(gains.device)], is_int64=is_int64,
+            gains=None if gains is None else gains.reshape(-1)[gi.to(gains.device)], is_int64=is_int64, verify=verify,
         )
     return out
 
@@ -1151,7 +1151,7 @@ def decode_flac_device(compressed, starts, nbytes, stream_size, first_sample=-1,
                     last_sample, None, _dp(out), _dp(offsets), _dp(gains), _stream_ptr(), vfy,
                 )
         if errcode != 0:
-            return _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, True)
+            return _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, True, verify)
         return out
     with _on_device(dev):
         if offsets is None:
@@ -1169,7 +1169,7 @@ def decode_flac_device(compressed, starts, nbytes, stream_size, first_sample=-1,
                 None, _dp(out), _dp(offsets), _dp(gains), _stream_ptr(), vfy,
             )
     if errcode != 0:
-        return _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, False)
+        return _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, False, verify)
     return out
 
 
