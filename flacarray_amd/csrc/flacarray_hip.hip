@@ -275,97 +275,152 @@ int get_crc_tab_fused(const uint16_t** out) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-struct EncodePlan {
+// ---- the encode driver's plan: what every encode sequence, size query and splice derives from a geometry ----
+// Validation in the order of the reference's encode() (compress.c:144-152), then the two limits of the format and the
+// grid.  On FA_ERROR_ENCODE_PROCESS (a limit) P, B, nf and tail_bs are set; on the argument errors nothing is.
+struct FramePlan {
     LevelParams P;
-    int64_t nf, F;
-    int tail_bs;
-    size_t off_slots, off_fbytes, off_foff, off_snb, off_total, total;
-    int64_t slot_stride;
+    uint32_t level;
+    int nch;
+    int64_t n_stream, stream_size;
+    int64_t B, nf, F, hb;  // block size, frames per stream, frames, stream header bytes
+    int tail_bs;           // samples of a stream's last frame
+    int64_t slot_stride;   // one slot per frame: kSlotBytes per channel
+    int64_t capacity;      // every frame VERBATIM: one slot per frame and channel + the stream headers
+    int32_t pmax_full, pmax_tail;     // max_porder_for(B / tail_bs, max_porder, 0)
+    double escale_full, escale_tail;  // 0.5 / blocksize
 };
 
-int make_plan(int64_t n_stream, int64_t stream_size, uint32_t level, EncodePlan* pl, int nch = 1) {
+int make_frame_plan(int64_t n_stream, int64_t stream_size, uint32_t level, int nch, FramePlan* fp) {
     if (level > 8) return FA_ERROR_INVALID_LEVEL;
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
-    pl->P = level_params(level);
-    const int64_t B = pl->P.blocksize;
-    pl->nf = (stream_size + B - 1) / B;
-    pl->tail_bs = (int)(stream_size - (pl->nf - 1) * B);
-    if (18 * pl->nf >= (1 << 24)) return FA_ERROR_ENCODE_PROCESS;  // SEEKTABLE block length is 24 bit
-    if (pl->nf > 0x7fffffffLL / n_stream) return FA_ERROR_ENCODE_PROCESS;  // grid limit; host API chunks
-    pl->F = n_stream * pl->nf;
-    size_t o = 0;
-    pl->slot_stride = (int64_t)kSlotBytes * nch;
-    pl->off_slots = o;  o = align_up(o + (size_t)pl->F * (size_t)pl->slot_stride, 256);
-    pl->off_fbytes = o; o = align_up(o + (size_t)pl->F * 4, 256);
-    pl->off_foff = o;   o = align_up(o + (size_t)pl->F * 8, 256);
-    pl->off_snb = o;    o = align_up(o + (size_t)n_stream * 8, 256);
-    pl->off_total = o;  o = align_up(o + 8, 256);
-    pl->total = o + 4096;  // slack: the compaction kernel reads whole groups of 256-byte blocks past a frame's end
+    fp->P = level_params(level);
+    fp->level = level; fp->nch = nch; fp->n_stream = n_stream; fp->stream_size = stream_size;
+    fp->B = fp->P.blocksize;
+    fp->nf = (stream_size + fp->B - 1) / fp->B;
+    fp->tail_bs = (int)(stream_size - (fp->nf - 1) * fp->B);
+    if (18 * fp->nf >= (1 << 24)) return FA_ERROR_ENCODE_PROCESS;  // SEEKTABLE block length is 24 bit
+    if (fp->nf > 0x7fffffffLL / n_stream) return FA_ERROR_ENCODE_PROCESS;  // 32-bit frame numbers (the grid; K3G's tickets: + its grid, still 32 bit); the host API chunks
+    fp->F = n_stream * fp->nf;
+    fp->hb = stream_header_bytes(fp->nf);
+    fp->slot_stride = (int64_t)kSlotBytes * nch;
+    fp->capacity = fp->F * fp->slot_stride + n_stream * fp->hb;
+    fp->pmax_full = max_porder_for((int)fp->B, fp->P.max_porder, 0);
+    fp->pmax_tail = max_porder_for(fp->tail_bs, fp->P.max_porder, 0);
+    fp->escale_full = 0.5 / (double)fp->B;
+    fp->escale_tail = 0.5 / (double)fp->tail_bs;
     return FA_ERROR_NONE;
+}
+
+// the slot sequence (K3 + K4 + K5): a slot per frame, the frame sizes and offsets, the stream sizes, the total
+struct SlotLayout {
+    size_t off_slots, off_fbytes, off_foff, off_snb, off_total, total;
+};
+SlotLayout slot_layout(const FramePlan& fp) {
+    SlotLayout l;
+    size_t o = 0;
+    l.off_slots = o;  o = align_up(o + (size_t)fp.F * (size_t)fp.slot_stride, 256);
+    l.off_fbytes = o; o = align_up(o + (size_t)fp.F * 4, 256);
+    l.off_foff = o;   o = align_up(o + (size_t)fp.F * 8, 256);
+    l.off_snb = o;    o = align_up(o + (size_t)fp.n_stream * 8, 256);
+    l.off_total = o;  o = align_up(o + 8, 256);
+    l.total = o + 4096;  // slack: the compaction kernel reads whole groups of 256-byte blocks past a frame's end
+    return l;
 }
 
 template <int MLO, int NCH>
 void launch_encode(const EncodeArgs& a, int64_t F, hipStream_t st) {
     hipLaunchKernelGGL((encode_frames_kernel<MLO, NCH>), dim3((unsigned)F), dim3(64), 0, st, a);
 }
+// K3 by the level's maximal LPC order and the channel count, `grid` workgroups
+void launch_encode_for(const EncodeArgs& a, int nch, int64_t grid, hipStream_t st) {
+#ifdef FA_DEV_MINIMAL  // diagnostic builds (seconds instead of minutes to compile): level 3-5 int32 kernels only
+    (void)nch;
+    launch_encode<8, 1>(a, grid, st);
+#else
+    if (nch == 1) {
+        switch (a.max_lpc_order) {
+            case 0: launch_encode<0, 1>(a, grid, st); break;
+            case 6: launch_encode<6, 1>(a, grid, st); break;
+            case 8: launch_encode<8, 1>(a, grid, st); break;
+            default: launch_encode<12, 1>(a, grid, st); break;
+        }
+    } else {
+        switch (a.max_lpc_order) {
+            case 0: launch_encode<0, 2>(a, grid, st); break;
+            case 6: launch_encode<6, 2>(a, grid, st); break;
+            case 8: launch_encode<8, 2>(a, grid, st); break;
+            default: launch_encode<12, 2>(a, grid, st); break;
+        }
+    }
+#endif
+}
+
+// The publish block of the single-pass encoders' workspace (K3F and K3G): frame sizes and absolute offsets, then the
+// words the kernels publish through -- sizes, offsets, and 256 bytes that hold the ticket word (+0), the error flags
+// (+8), K3F's NaN flag (+12) and the scanner's total (+16: next to the error word, one copy brings all three back).
+struct PublishBlock {
+    size_t off_fbytes, off_fabs, off_zero, off_size, off_off, off_ticket, zero_bytes, off_total;
+};
+// lays the block out from offset 0 and returns its end
+size_t lay_publish_block(int64_t F, PublishBlock* b) {
+    size_t o = 0;
+    b->off_fbytes = o; o = align_up(o + (size_t)F * 4, 256);
+    b->off_fabs = o;   o = align_up(o + (size_t)F * 8, 256);
+    b->off_zero = o;   // everything from here to off_total is zeroed before every launch
+    b->off_size = o;   o = align_up(o + (size_t)F * 4, 256);
+    b->off_off = o;    o = align_up(o + (size_t)F * 8, 256);
+    b->off_ticket = o; o = align_up(o + 32, 256);
+    b->zero_bytes = o - b->off_zero;
+    b->off_total = o;  o = align_up(o + 8, 256);
+    return o;
+}
+void point_into_publish_block(const PublishBlock& b, char* ws, FusedArgs* a) {
+    a->frame_bytes = reinterpret_cast<uint32_t*>(ws + b.off_fbytes);
+    a->frame_abs = reinterpret_cast<int64_t*>(ws + b.off_fabs);
+    a->size_pub = reinterpret_cast<uint32_t*>(ws + b.off_size);
+    a->off_pub = reinterpret_cast<unsigned long long*>(ws + b.off_off);
+    a->ticket = reinterpret_cast<uint32_t*>(ws + b.off_ticket);
+    a->err = reinterpret_cast<int*>(ws + b.off_ticket + 8);
+    a->total = reinterpret_cast<int64_t*>(ws + b.off_ticket + 16);
+}
 
 // ---- single-pass encode (encode_fused.hpp): every frame is a full 4096-sample mono frame ----
-struct FusedPlan {
-    LevelParams P;
-    int64_t nf, F, hb;
-    size_t off_fbytes, off_fabs, off_zero, off_size, off_off, off_ticket, zero_bytes, off_total, total;
+struct FusedLayout {
+    PublishBlock pub;
     size_t off_tslots, off_tbytes, off_toff, off_tzero;  // short last frames: slots and the compaction's arguments
-    int tail_bs;
-    int64_t capacity;
+    size_t total;
 };
 
 static bool slots_forced() { return std::getenv("FLACARRAY_HIP_SLOTS") != nullptr; }  // diagnostic: K3 + K4 + K5 for everything
 // f32: float32 input (quantised in the staging load of K3F only: whole frames).  int32 streams may end in a short
 // frame -- the slot encoder writes those, K3F the rest -- if every frame still starts on a 16-byte boundary.
-bool fused_geometry(int64_t n_stream, int64_t stream_size, uint32_t level, bool f32 = false) {
-    if (level < 3 || level > 8 || n_stream <= 0 || stream_size <= 0) return false;
-    if (stream_size % kMaxBlock != 0 && (f32 || stream_size % 4 != 0 || stream_size < 2 * kMaxBlock)) return false;
-    const int64_t nf = (stream_size + kMaxBlock - 1) / kMaxBlock;
-    if (18 * nf >= (1 << 24)) return false;
-    if (nf > 0x7fffffffLL / n_stream) return false;
+bool fused_geometry(const FramePlan& fp, bool f32 = false) {
+    if (fp.level < 3 || fp.nch != 1) return false;
+    if (fp.tail_bs != kMaxBlock && (f32 || fp.stream_size % 4 != 0 || fp.stream_size < 2 * kMaxBlock)) return false;
     return !slots_forced();
 }
 
-void make_fused_plan(int64_t n_stream, int64_t stream_size, uint32_t level, FusedPlan* pl) {
-    pl->P = level_params(level);
-    pl->nf = (stream_size + kMaxBlock - 1) / kMaxBlock;
-    pl->tail_bs = (int)(stream_size - (pl->nf - 1) * (int64_t)kMaxBlock);
-    pl->F = n_stream * pl->nf;
-    pl->hb = stream_header_bytes(pl->nf);
-    size_t o = 0;
-    pl->off_fbytes = o; o = align_up(o + (size_t)pl->F * 4, 256);
-    pl->off_fabs = o;   o = align_up(o + (size_t)pl->F * 8, 256);
-    pl->off_zero = o;   // everything from here to off_total is zeroed before every launch
-    pl->off_size = o;   o = align_up(o + (size_t)pl->F * 4, 256);
-    pl->off_off = o;    o = align_up(o + (size_t)pl->F * 8, 256);
-    pl->off_ticket = o; o = align_up(o + 16, 256);  // ticket word, error flags
-    pl->zero_bytes = o - pl->off_zero;
-    pl->off_total = o;  o = align_up(o + 8, 256);
-    pl->off_tslots = pl->off_tbytes = pl->off_toff = pl->off_tzero = o;
-    if (pl->tail_bs != kMaxBlock) {
-        pl->off_tslots = o; o = align_up(o + (size_t)n_stream * (size_t)kSlotBytes + 4096, 256);  // (+ the compaction's group reads)
-        pl->off_tbytes = o; o = align_up(o + (size_t)n_stream * 4, 256);
-        pl->off_toff = o;   o = align_up(o + (size_t)n_stream * 8, 256);
-        pl->off_tzero = o;  o = align_up(o + (size_t)n_stream * 8, 256);
+FusedLayout fused_layout(const FramePlan& fp) {
+    FusedLayout l;
+    size_t o = lay_publish_block(fp.F, &l.pub);
+    l.off_tslots = l.off_tbytes = l.off_toff = l.off_tzero = o;
+    if (fp.tail_bs != kMaxBlock) {
+        l.off_tslots = o; o = align_up(o + (size_t)fp.n_stream * (size_t)kSlotBytes + 4096, 256);  // (+ the compaction's group reads)
+        l.off_tbytes = o; o = align_up(o + (size_t)fp.n_stream * 4, 256);
+        l.off_toff = o;   o = align_up(o + (size_t)fp.n_stream * 8, 256);
+        l.off_tzero = o;  o = align_up(o + (size_t)fp.n_stream * 8, 256);
     }
-    pl->total = o;
-    pl->capacity = pl->F * (int64_t)kSlotBytes + n_stream * pl->hb;
+    l.total = o;
+    return l;
 }
 
 
 // ---- single-pass encode of every other geometry (encode_placed.hpp): K3's frame body, frames placed by their waves ----
-struct PlacedPlan {
-    LevelParams P;
-    int64_t nf, F, hb, slot_stride;
-    int tail_bs;
-    size_t off_fbytes, off_fabs, off_zero, off_size, off_off, off_ticket, zero_bytes, off_total, off_slots, total;
-    int64_t capacity;
+struct PlacedLayout {
+    PublishBlock pub;
+    size_t off_slots, total;
 };
 
 // the persistent grid (+ the scanner's workgroup), never more than frames + scanner
@@ -379,34 +434,14 @@ int64_t placed_grid(int64_t F) {
     return std::min<int64_t>(g, F) + 1;
 }
 
-int make_placed_plan(int64_t n_stream, int64_t stream_size, uint32_t level, int nch, PlacedPlan* pl) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
-    pl->P = level_params(level);
-    const int64_t B = pl->P.blocksize;
-    pl->nf = (stream_size + B - 1) / B;
-    pl->tail_bs = (int)(stream_size - (pl->nf - 1) * B);
-    if (18 * pl->nf >= (1 << 24)) return FA_ERROR_ENCODE_PROCESS;  // SEEKTABLE block length is 24 bit
-    if (pl->nf > 0x7fffffffLL / n_stream) return FA_ERROR_ENCODE_PROCESS;  // 32-bit frame numbers (tickets: + the grid, still 32 bit); the host API chunks
-    pl->F = n_stream * pl->nf;
-    pl->hb = stream_header_bytes(pl->nf);
-    pl->slot_stride = (int64_t)kSlotBytes * nch;
+PlacedLayout placed_layout(const FramePlan& fp) {
+    PlacedLayout l;
     // (slots sized for the 1152-sample blocks of levels 0-2 -- 5 / 9.5 KB, L2 resident -- change nothing: 11.89 against 11.90 ms)
-    size_t o = 0;
-    pl->off_fbytes = o; o = align_up(o + (size_t)pl->F * 4, 256);
-    pl->off_fabs = o;   o = align_up(o + (size_t)pl->F * 8, 256);
-    pl->off_zero = o;   // everything from here to off_total is zeroed before every launch
-    pl->off_size = o;   o = align_up(o + (size_t)pl->F * 4, 256);
-    pl->off_off = o;    o = align_up(o + (size_t)pl->F * 8, 256);
-    pl->off_ticket = o; o = align_up(o + 32, 256);  // ticket word, error flags, the scanner's total
-    pl->zero_bytes = o - pl->off_zero;
-    pl->off_total = o;  o = align_up(o + 8, 256);
+    size_t o = lay_publish_block(fp.F, &l.pub);
     // two slots per workgroup of the persistent grid + the placement copy's reads past the last slot's end
-    pl->off_slots = o;  o = align_up(o + (size_t)placed_grid(pl->F) * 2 * (size_t)pl->slot_stride + 256 * (size_t)(FA_PG_GROUP) + 256, 256);
-    pl->total = o;
-    pl->capacity = pl->F * (int64_t)kSlotBytes * nch + n_stream * pl->hb;  // (the figure of the slot sequence, whatever the slots here)
-    return FA_ERROR_NONE;
+    l.off_slots = o;  o = align_up(o + (size_t)placed_grid(fp.F) * 2 * (size_t)fp.slot_stride + 256 * (size_t)(FA_PG_GROUP) + 256, 256);
+    l.total = o;
+    return l;
 }
 
 // optional CRC-16 check of every frame the decode just read (verify_kernels.hpp); h_err receives the refreshed flags
@@ -1101,100 +1136,112 @@ void fa_release_scratch(void) {
     ds_->pin_tried = false;
 }
 
-int64_t fa_encode_workspace_bytes(int64_t n_stream, int64_t stream_size, uint32_t level) {
-    EncodePlan pl;
-    if (make_plan(n_stream, stream_size, level, &pl) != FA_ERROR_NONE) return -1;
-    return (int64_t)pl.total;
+static int64_t slot_workspace_for(int64_t n_stream, int64_t stream_size, uint32_t level, int nch) {
+    FramePlan fp;
+    if (make_frame_plan(n_stream, stream_size, level, nch, &fp) != FA_ERROR_NONE) return -1;
+    return (int64_t)slot_layout(fp).total;
+}
+int64_t fa_encode_workspace_bytes(int64_t n_stream, int64_t stream_size, uint32_t level) { return slot_workspace_for(n_stream, stream_size, level, 1); }
+int64_t fa_encode_workspace_bytes_i64(int64_t n_stream, int64_t stream_size, uint32_t level) { return slot_workspace_for(n_stream, stream_size, level, 2); }
+
+// ---- the steps the three encode sequences share ----
+// K3's arguments from a plan: geometry, level parameters, both windows, the per-block-size constants, the caller's slots and
+// frame sizes.  hdr (frame_header_table) and stamps (stamps_scratch) are the caller's to set.
+static int fill_encode_args(const FramePlan& fp, const int32_t* d_data, uint8_t* slots, uint32_t* frame_bytes, int32_t* d_info, EncodeArgs* a) {
+    std::memset(a, 0, sizeof *a);
+    a->data = d_data; a->n_stream = fp.n_stream; a->stream_size = fp.stream_size; a->nframes = fp.nf;
+    a->B = (int32_t)fp.B; a->tail_bs = fp.tail_bs;
+    a->max_lpc_order = fp.P.max_lpc_order; a->max_porder = fp.P.max_porder; a->precision = fp.P.qlp_precision;
+    int rc = get_window(a->B, &a->win);
+    if (rc) return rc;
+    rc = get_window(a->tail_bs, &a->win_tail);
+    if (rc) return rc;
+    a->slots = slots;
+    a->slot_stride = fp.slot_stride;
+    a->frame_bytes = frame_bytes;
+    a->info = reinterpret_cast<FrameInfo*>(d_info);
+    a->pmax_full = fp.pmax_full; a->pmax_tail = fp.pmax_tail;
+    a->escale_full = fp.escale_full; a->escale_tail = fp.escale_tail;
+    return FA_ERROR_NONE;
 }
 
-int64_t fa_encode_workspace_bytes_i64(int64_t n_stream, int64_t stream_size, uint32_t level) {
-    EncodePlan pl;
-    if (make_plan(n_stream, stream_size, level, &pl, 2) != FA_ERROR_NONE) return -1;
-    return (int64_t)pl.total;
+// frame header fields by frame number: tabulated on the host, cached on the device (per-device state; the caller holds api_mu)
+static int frame_header_table(DeviceState* ds, const FramePlan& fp, hipStream_t st, const uint4** out) {
+    void* dp = nullptr;
+    const int B = (int)fp.B, nch = fp.nch;
+    const size_t ntab = (size_t)fp.nf * (nch == 2 ? 2 : 1);  // two-channel arrays: a second half with assignment side + right
+    int rc = get_scratch(9, ntab * sizeof(uint4) + 256, &dp);
+    if (rc) return rc;
+    if (ds->c_nf != fp.nf || ds->c_B != B || ds->c_tail != fp.tail_bs || ds->c_nch != nch || ds->c_dp != dp || ds->c_epoch != ds->scratch_epoch) {
+        ds->h_hdr.resize(ntab);
+        for (int64_t f = 0; f < fp.nf; ++f) {
+            ds->h_hdr[(size_t)f] = frame_header_entry((uint64_t)f, (f == fp.nf - 1) ? fp.tail_bs : B, nch);
+            if (nch == 2) ds->h_hdr[(size_t)(fp.nf + f)] = frame_header_entry((uint64_t)f, (f == fp.nf - 1) ? fp.tail_bs : B, nch, true);
+        }
+        FA_HIP_TRY(hipMemcpyAsync(dp, ds->h_hdr.data(), ntab * sizeof(uint4), hipMemcpyHostToDevice, st));
+        FA_HIP_TRY(hipStreamSynchronize(st));  // h_hdr is reused by the next call
+        ds->c_nf = fp.nf; ds->c_B = B; ds->c_tail = fp.tail_bs; ds->c_nch = nch; ds->c_dp = dp; ds->c_epoch = ds->scratch_epoch;
+    }
+    *out = reinterpret_cast<const uint4*>(dp);
+    return FA_ERROR_NONE;
 }
 
+// diagnostic build (-DFA_STAMPS): the per-phase cycle sums' scratch (fa_debug_stamps), null in every other build
+static unsigned long long* stamps_scratch(DeviceState* ds) {
+#ifdef FA_STAMPS
+    void* sp = nullptr;
+    if (get_scratch(6, 512, &sp) == 0) {
+        if (!ds->stamps_zeroed) { (void)hipMemset(sp, 0, 512); ds->stamps_zeroed = true; }
+        return reinterpret_cast<unsigned long long*>(sp);
+    }
+#else
+    (void)ds;
+#endif
+    return nullptr;
+}
+
+// What a single-pass kernel left at +8 of the ticket block: one copy and one stream synchronisation bring the error
+// word, K3F's NaN flag and the scanner's total (headers and short frames included) back; a blob that does not fit the
+// caller's buffer is FA_ERROR_ALLOC, any other flag FA_ERROR_ENCODE_PROCESS.
+struct PublishBack { int32_t err, nan; int64_t total; };
+static_assert(sizeof(PublishBack) == 16, "error word at +8, NaN flag at +12, total at +16 of the ticket block");
+static int read_publish_back(const FusedArgs& a, hipStream_t st, PublishBack* back) {
+    FA_HIP_TRY(hipMemcpyAsync(back, a.err, sizeof *back, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    if (back->err == 1 || (back->err == 0 && back->total > a.capacity)) return FA_ERROR_ALLOC;  // the blob does not fit the caller's buffer
+    if (back->err) {
+        std::fprintf(stderr, "flacarray_hip: single-pass encode failed (flags %d: 1 = offset outside the buffer, 2 = a frame timed out waiting for its offset, 4 = the scanner timed out)\n", back->err);
+        return FA_ERROR_ENCODE_PROCESS;
+    }
+    return FA_ERROR_NONE;
+}
+
+// ---- the slot sequence: K3 into a slot per frame, K4 (sizes -> offsets, one wait for the total), then K5 into the caller's blob ----
 static int encode_device_begin(const int32_t* d_data, int nch, int64_t n_stream, int64_t stream_size, uint32_t level,
                                void* d_workspace, int64_t workspace_bytes, int64_t* d_starts, int64_t* d_nbytes,
                                int64_t* h_total_bytes, int32_t* d_info, void* stream) {
     FA_API_LOCK;
-    EncodePlan pl;
-    int rc = make_plan(n_stream, stream_size, level, &pl, nch);
+    FramePlan fp;
+    int rc = make_frame_plan(n_stream, stream_size, level, nch, &fp);
     if (rc) return rc;
+    const SlotLayout pl = slot_layout(fp);
     if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(d_workspace);
     prof_begin(3, st);
     EncodeArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.data = d_data; a.n_stream = n_stream; a.stream_size = stream_size; a.nframes = pl.nf;
-    a.B = pl.P.blocksize; a.tail_bs = pl.tail_bs;
-    a.max_lpc_order = pl.P.max_lpc_order; a.max_porder = pl.P.max_porder; a.precision = pl.P.qlp_precision;
-    rc = get_window(a.B, &a.win);
+    rc = fill_encode_args(fp, d_data, reinterpret_cast<uint8_t*>(ws + pl.off_slots), reinterpret_cast<uint32_t*>(ws + pl.off_fbytes), d_info, &a);
     if (rc) return rc;
-    rc = get_window(a.tail_bs, &a.win_tail);
+    rc = frame_header_table(ds_, fp, st, &a.hdr);
     if (rc) return rc;
-    a.slots = reinterpret_cast<uint8_t*>(ws + pl.off_slots);
-    a.slot_stride = pl.slot_stride;
-    a.frame_bytes = reinterpret_cast<uint32_t*>(ws + pl.off_fbytes);
-    a.info = reinterpret_cast<FrameInfo*>(d_info);
-    a.stamps = nullptr;
-    a.pmax_full = max_porder_for(a.B, a.max_porder, 0);
-    a.pmax_tail = max_porder_for(a.tail_bs, a.max_porder, 0);
-    a.escale_full = 0.5 / (double)a.B;
-    a.escale_tail = 0.5 / (double)a.tail_bs;
-    {
-        // frame header fields by frame number: tabulated on the host, cached on the device (per-device state)
-        void* dp = nullptr;
-        const size_t ntab = (size_t)pl.nf * (nch == 2 ? 2 : 1);  // two-channel arrays: a second half with assignment side + right
-        rc = get_scratch(9, ntab * sizeof(uint4) + 256, &dp);
-        if (rc) return rc;
-        if (ds_->c_nf != pl.nf || ds_->c_B != a.B || ds_->c_tail != a.tail_bs || ds_->c_nch != nch || ds_->c_dp != dp ||
-            ds_->c_epoch != ds_->scratch_epoch) {
-            ds_->h_hdr.resize(ntab);
-            for (int64_t f = 0; f < pl.nf; ++f) {
-                ds_->h_hdr[(size_t)f] = frame_header_entry((uint64_t)f, (f == pl.nf - 1) ? a.tail_bs : a.B, nch);
-                if (nch == 2) ds_->h_hdr[(size_t)(pl.nf + f)] = frame_header_entry((uint64_t)f, (f == pl.nf - 1) ? a.tail_bs : a.B, nch, true);
-            }
-            FA_HIP_TRY(hipMemcpyAsync(dp, ds_->h_hdr.data(), ntab * sizeof(uint4), hipMemcpyHostToDevice, st));
-            FA_HIP_TRY(hipStreamSynchronize(st));  // h_hdr is reused by the next call
-            ds_->c_nf = pl.nf; ds_->c_B = a.B; ds_->c_tail = a.tail_bs; ds_->c_nch = nch; ds_->c_dp = dp; ds_->c_epoch = ds_->scratch_epoch;
-        }
-        a.hdr = reinterpret_cast<const uint4*>(dp);
-    }
-#ifdef FA_STAMPS
-    {
-        void* sp = nullptr;
-        if (get_scratch(6, 512, &sp) == 0) {
-            if (!ds_->stamps_zeroed) { (void)hipMemset(sp, 0, 512); ds_->stamps_zeroed = true; }
-            a.stamps = reinterpret_cast<unsigned long long*>(sp);
-        }
-    }
-#endif
+    a.stamps = stamps_scratch(ds_);
     prof_begin(0, st);
-#ifdef FA_DEV_MINIMAL  // diagnostic builds (seconds instead of minutes to compile): level 3-5 int32 kernels only
-    launch_encode<8, 1>(a, pl.F, st);
-#else
-    if (nch == 1) {
-        switch (a.max_lpc_order) {
-            case 0: launch_encode<0, 1>(a, pl.F, st); break;
-            case 6: launch_encode<6, 1>(a, pl.F, st); break;
-            case 8: launch_encode<8, 1>(a, pl.F, st); break;
-            default: launch_encode<12, 1>(a, pl.F, st); break;
-        }
-    } else {
-        switch (a.max_lpc_order) {
-            case 0: launch_encode<0, 2>(a, pl.F, st); break;
-            case 6: launch_encode<6, 2>(a, pl.F, st); break;
-            case 8: launch_encode<8, 2>(a, pl.F, st); break;
-            default: launch_encode<12, 2>(a, pl.F, st); break;
-        }
-    }
-#endif
+    launch_encode_for(a, nch, fp.F, st);
     prof_end(0, st);
     int64_t* d_foff = reinterpret_cast<int64_t*>(ws + pl.off_foff);
     int64_t* d_snb = reinterpret_cast<int64_t*>(ws + pl.off_snb);
     int64_t* d_total = reinterpret_cast<int64_t*>(ws + pl.off_total);
-    hipLaunchKernelGGL(stream_scan_kernel, dim3((unsigned)n_stream), dim3(256), 0, st, a.frame_bytes, pl.nf, d_foff, d_snb);
+    hipLaunchKernelGGL(stream_scan_kernel, dim3((unsigned)n_stream), dim3(256), 0, st, a.frame_bytes, fp.nf, d_foff, d_snb);
     hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_snb, n_stream, d_starts, d_total);
     FA_HIP_TRY(hipMemcpyAsync(d_nbytes, d_snb, (size_t)n_stream * 8, hipMemcpyDeviceToDevice, st));
     FA_HIP_TRY(hipMemcpyAsync(h_total_bytes, d_total, 8, hipMemcpyDeviceToHost, st));
@@ -1220,26 +1267,26 @@ int fa_encode_i64_device_begin(const int64_t* d_data, int64_t n_stream, int64_t 
 static int encode_device_finish(int nch, int64_t n_stream, int64_t stream_size, uint32_t level, void* d_workspace,
                                 const int64_t* d_starts, unsigned char* d_bytes, void* stream) {
     FA_API_LOCK;
-    EncodePlan pl;
-    int rc = make_plan(n_stream, stream_size, level, &pl, nch);
+    FramePlan fp;
+    int rc = make_frame_plan(n_stream, stream_size, level, nch, &fp);
     if (rc) return rc;
+    const SlotLayout pl = slot_layout(fp);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(d_workspace);
     const uint16_t* crc = nullptr;
     rc = get_crc_tab(&crc);
     if (rc) return rc;
     const int64_t* d_foff = reinterpret_cast<const int64_t*>(ws + pl.off_foff);
-    launch_write_headers(st, n_stream, d_bytes, d_starts, d_foff, pl.nf, stream_size, (int32_t)pl.P.blocksize, (int32_t)pl.tail_bs,
-                         (int32_t)nch);
-    int64_t nblk = (pl.F + 3) / 4;
+    launch_write_headers(st, n_stream, d_bytes, d_starts, d_foff, fp.nf, stream_size, (int32_t)fp.B, (int32_t)fp.tail_bs, (int32_t)nch);
+    int64_t nblk = (fp.F + 3) / 4;
 #ifndef FA_K5_MAXBLK
 #define FA_K5_MAXBLK 32768
 #endif
     if (nblk > FA_K5_MAXBLK) nblk = FA_K5_MAXBLK;
     prof_begin(1, st);
     launch_compact_frames(st, nblk, reinterpret_cast<const uint8_t*>(ws + pl.off_slots),
-                          reinterpret_cast<const uint32_t*>(ws + pl.off_fbytes), d_foff, d_starts, pl.nf, pl.F, crc, d_bytes,
-                          pl.slot_stride);
+                          reinterpret_cast<const uint32_t*>(ws + pl.off_fbytes), d_foff, d_starts, fp.nf, fp.F, crc, d_bytes,
+                          fp.slot_stride);
     prof_end(1, st);
     prof_end(3, st);
     FA_HIP_TRY(hipGetLastError());
@@ -1258,31 +1305,31 @@ int fa_encode_i64_device_finish(int64_t n_stream, int64_t stream_size, uint32_t 
 
 // Every valid geometry has a single-pass encoder: K3F (full mono frames of levels 3-8) or K3G (the rest).
 int fa_encode_single_pass_supported(int64_t n_stream, int64_t stream_size, uint32_t level) {
-    PlacedPlan pl;
-    return (make_placed_plan(n_stream, stream_size, level, 1, &pl) == FA_ERROR_NONE && !slots_forced()) ? 1 : 0;
+    FramePlan fp;
+    return (make_frame_plan(n_stream, stream_size, level, 1, &fp) == FA_ERROR_NONE && !slots_forced()) ? 1 : 0;
 }
 
 static int64_t capacity_bytes_for(int64_t n_stream, int64_t stream_size, uint32_t level, int nch) {
-    PlacedPlan pl;
-    if (make_placed_plan(n_stream, stream_size, level, nch, &pl) != FA_ERROR_NONE) return -1;
-    return pl.capacity;  // every frame VERBATIM: one slot per frame and channel + the stream headers (K3F's figure is the same)
+    FramePlan fp;
+    if (make_frame_plan(n_stream, stream_size, level, nch, &fp) != FA_ERROR_NONE) return -1;
+    return fp.capacity;  // (the figure of the slot sequence, of K3F and of K3G, whatever their slots)
 }
 int64_t fa_encode_capacity_bytes(int64_t n_stream, int64_t stream_size, uint32_t level) { return capacity_bytes_for(n_stream, stream_size, level, 1); }
 int64_t fa_encode_capacity_bytes_i64(int64_t n_stream, int64_t stream_size, uint32_t level) { return capacity_bytes_for(n_stream, stream_size, level, 2); }
 
 // The workspace serves whichever sequence the call takes: K3F's, K3G's (also what K3F's geometries take when the rows
-// are not 16-byte aligned), or -- FLACARRAY_HIP_SLOTS -- the slot sequence's.
-static int64_t single_pass_workspace_for(int64_t n_stream, int64_t stream_size, uint32_t level, int nch) {
-    if (slots_forced()) return nch == 2 ? fa_encode_workspace_bytes_i64(n_stream, stream_size, level) : fa_encode_workspace_bytes(n_stream, stream_size, level);
-    PlacedPlan pp;
-    if (make_placed_plan(n_stream, stream_size, level, nch, &pp) != FA_ERROR_NONE) return -1;
-    int64_t need = (int64_t)pp.total;
-    if (nch == 1 && fused_geometry(n_stream, stream_size, level)) {
-        FusedPlan pl;
-        make_fused_plan(n_stream, stream_size, level, &pl);
-        need = std::max<int64_t>(need, (int64_t)pl.total);
-    }
+// are not 16-byte aligned), or -- FLACARRAY_HIP_SLOTS -- the slot sequence's.  Both single-pass sequences ask their
+// caller for this figure, the one the query answers, not for their own share of it: whether a short workspace is
+// refused does not depend on the route the call takes.
+static int64_t single_pass_need(const FramePlan& fp) {
+    int64_t need = (int64_t)placed_layout(fp).total;
+    if (fused_geometry(fp)) need = std::max<int64_t>(need, (int64_t)fused_layout(fp).total);
     return need;
+}
+static int64_t single_pass_workspace_for(int64_t n_stream, int64_t stream_size, uint32_t level, int nch) {
+    FramePlan fp;
+    if (make_frame_plan(n_stream, stream_size, level, nch, &fp) != FA_ERROR_NONE) return -1;
+    return slots_forced() ? (int64_t)slot_layout(fp).total : single_pass_need(fp);
 }
 int64_t fa_encode_single_pass_workspace_bytes(int64_t n_stream, int64_t stream_size, uint32_t level) {
     return single_pass_workspace_for(n_stream, stream_size, level, 1);
@@ -1292,23 +1339,22 @@ int64_t fa_encode_single_pass_workspace_bytes_i64(int64_t n_stream, int64_t stre
 }
 
 // the single-pass sequence: (float32 input: range pre-pass K1a/K1b,) zero the publish words, K3F, stream headers
-static int fused_encode_run(const void* d_data, bool f32, const float* d_quanta, float* d_offsets, float* d_gains, int64_t n_stream,
-                            int64_t stream_size, uint32_t level, void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes,
-                            int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info,
-                            void* stream) {
+static int fused_encode_run(const FramePlan& fp, const void* d_data, bool f32, const float* d_quanta, float* d_offsets, float* d_gains,
+                            void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
+                            int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info, void* stream) {
     FA_API_LOCK;
-    FusedPlan pl;
-    make_fused_plan(n_stream, stream_size, level, &pl);
-    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
+    const FusedLayout pl = fused_layout(fp);
+    const int64_t n_stream = fp.n_stream, stream_size = fp.stream_size;
+    if (!d_workspace || workspace_bytes < single_pass_need(fp)) return FA_ERROR_ALLOC;
     // The buffer may be smaller than the worst case (every frame VERBATIM): a frame whose offset lies outside it is not
     // written and the call reports FA_ERROR_ALLOC -- the caller gambles on its data's compressibility and retries with
     // fa_encode_capacity_bytes() if it loses.  It must at least hold the stream headers.
-    if (!d_bytes || capacity_bytes < n_stream * pl.hb + 64) return FA_ERROR_ALLOC;
+    if (!d_bytes || capacity_bytes < n_stream * fp.hb + 64) return FA_ERROR_ALLOC;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(d_workspace);
     prof_begin(3, st);
-    int* d_nanflag = reinterpret_cast<int*>(ws + pl.off_ticket + 12);  // (inside the zeroed region)
-    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_zero, 0, pl.zero_bytes, st));
+    int* d_nanflag = reinterpret_cast<int*>(ws + pl.pub.off_ticket + 12);  // (inside the zeroed region)
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.pub.off_zero, 0, pl.pub.zero_bytes, st));
     if (f32) {
         const int64_t cps = (stream_size + kRangeChunk - 1) / kRangeChunk;
         void* pp = nullptr;
@@ -1325,99 +1371,50 @@ static int fused_encode_run(const void* d_data, bool f32, const float* d_quanta,
     }
     FusedArgs a;
     std::memset(&a, 0, sizeof a);
-    a.data = reinterpret_cast<const int32_t*>(d_data); a.f_offsets = d_offsets; a.f_gains = d_gains; a.n_stream = n_stream; a.stream_size = stream_size; a.nframes = pl.nf; a.total_frames = pl.F;
-    a.max_lpc_order = pl.P.max_lpc_order; a.max_porder = pl.P.max_porder; a.precision = pl.P.qlp_precision;
-    a.pmax_full = max_porder_for(kMaxBlock, a.max_porder, 0);
-    a.escale_full = 0.5 / (double)kMaxBlock;
-    a.tail_bs = pl.tail_bs;
-    const bool tails = (pl.tail_bs != kMaxBlock);
+    a.data = reinterpret_cast<const int32_t*>(d_data); a.f_offsets = d_offsets; a.f_gains = d_gains; a.n_stream = n_stream; a.stream_size = stream_size; a.nframes = fp.nf; a.total_frames = fp.F;
+    a.max_lpc_order = fp.P.max_lpc_order; a.max_porder = fp.P.max_porder; a.precision = fp.P.qlp_precision;
+    a.pmax_full = fp.pmax_full;
+    a.escale_full = fp.escale_full;
+    a.tail_bs = fp.tail_bs;
+    const bool tails = (fp.tail_bs != kMaxBlock);
     int rc = get_window(kMaxBlock, &a.win);
     if (rc) return rc;
     rc = get_crc_tab_fused(&a.crc_tab);
     if (rc) return rc;
-    {
-        void* dp = nullptr;
-        rc = get_scratch(9, (size_t)pl.nf * sizeof(uint4) + 256, &dp);
-        if (rc) return rc;
-        if (ds_->c_nf != pl.nf || ds_->c_B != kMaxBlock || ds_->c_tail != pl.tail_bs || ds_->c_nch != 1 || ds_->c_dp != dp ||
-            ds_->c_epoch != ds_->scratch_epoch) {
-            ds_->h_hdr.resize((size_t)pl.nf);
-            for (int64_t f = 0; f < pl.nf; ++f)
-                ds_->h_hdr[(size_t)f] = frame_header_entry((uint64_t)f, (f == pl.nf - 1) ? pl.tail_bs : kMaxBlock, 1);
-            FA_HIP_TRY(hipMemcpyAsync(dp, ds_->h_hdr.data(), (size_t)pl.nf * sizeof(uint4), hipMemcpyHostToDevice, st));
-            FA_HIP_TRY(hipStreamSynchronize(st));
-            ds_->c_nf = pl.nf; ds_->c_B = kMaxBlock; ds_->c_tail = pl.tail_bs; ds_->c_nch = 1; ds_->c_dp = dp; ds_->c_epoch = ds_->scratch_epoch;
-        }
-        a.hdr = reinterpret_cast<const uint4*>(dp);
-    }
-    a.blob = d_bytes; a.capacity = capacity_bytes; a.hb = pl.hb;
-    a.frame_bytes = reinterpret_cast<uint32_t*>(ws + pl.off_fbytes);
-    a.frame_abs = reinterpret_cast<int64_t*>(ws + pl.off_fabs);
+    rc = frame_header_table(ds_, fp, st, &a.hdr);
+    if (rc) return rc;
+    a.blob = d_bytes; a.capacity = capacity_bytes; a.hb = fp.hb;
+    point_into_publish_block(pl.pub, ws, &a);
     a.info = reinterpret_cast<FrameInfo*>(d_info);
-    a.size_pub = reinterpret_cast<uint32_t*>(ws + pl.off_size);
-    a.off_pub = reinterpret_cast<unsigned long long*>(ws + pl.off_off);
-    a.total = reinterpret_cast<int64_t*>(ws + pl.off_ticket + 16);  // (next to the error and NaN words: one copy brings all three back)
-    a.ticket = reinterpret_cast<uint32_t*>(ws + pl.off_ticket);
-    a.err = reinterpret_cast<int*>(ws + pl.off_ticket + 8);
-#ifdef FA_STAMPS
-    {
-        void* sp = nullptr;
-        if (get_scratch(6, 512, &sp) == 0) {
-            if (!ds_->stamps_zeroed) { (void)hipMemset(sp, 0, 512); ds_->stamps_zeroed = true; }
-            a.stamps = reinterpret_cast<unsigned long long*>(sp);
-        }
-    }
-#endif
+    a.stamps = stamps_scratch(ds_);
     if (tails) {
         // the short last frame of every stream: the slot encoder (one workgroup per stream) writes it to a slot and its
         // size goes into size_pub, so that the scanner places it between its neighbours like any other frame
         EncodeArgs t;
-        std::memset(&t, 0, sizeof t);
-        t.data = a.data; t.n_stream = n_stream; t.stream_size = stream_size; t.nframes = pl.nf; t.B = kMaxBlock; t.tail_bs = pl.tail_bs;
-        t.max_lpc_order = a.max_lpc_order; t.max_porder = a.max_porder; t.precision = a.precision;
-        t.win = a.win;
-        rc = get_window(pl.tail_bs, &t.win_tail);
+        rc = fill_encode_args(fp, a.data, reinterpret_cast<uint8_t*>(ws + pl.off_tslots), a.frame_bytes, d_info, &t);
         if (rc) return rc;
-        t.slots = reinterpret_cast<uint8_t*>(ws + pl.off_tslots); t.slot_stride = kSlotBytes;
-        t.frame_bytes = a.frame_bytes; t.info = a.info; t.hdr = a.hdr;
-        t.pmax_full = a.pmax_full; t.pmax_tail = max_porder_for(pl.tail_bs, a.max_porder, 0);
-        t.escale_full = a.escale_full; t.escale_tail = 0.5 / (double)pl.tail_bs;
+        t.hdr = a.hdr;
         t.tail_only = 1;
-#ifdef FA_DEV_MINIMAL
-        launch_encode<8, 1>(t, n_stream, st);
-#else
-        switch (t.max_lpc_order) {
-            case 6: launch_encode<6, 1>(t, n_stream, st); break;
-            case 8: launch_encode<8, 1>(t, n_stream, st); break;
-            default: launch_encode<12, 1>(t, n_stream, st); break;
-        }
-#endif
-        launch_fused_tail_publish(st, a.frame_bytes, a.size_pub, n_stream, pl.nf);
+        launch_encode_for(t, 1, n_stream, st);
+        launch_fused_tail_publish(st, a.frame_bytes, a.size_pub, n_stream, fp.nf);
     }
     prof_begin(0, st);
     launch_fused_encode(st, a, f32);
     prof_end(0, st);
-    struct { int32_t err, nan; int64_t total; } back = {0, 0, 0};
-    static_assert(sizeof back == 16, "error word at +8, NaN flag at +12, total at +16 of the ticket block");
-    {
-        // A frame that was dropped (no offset in time, or an offset outside the buffer) leaves frame_abs / off_pub of
-        // itself -- and, after a scanner time-out, of every frame behind it -- unwritten: the kernels below would
-        // turn those into addresses.  They run only after the error word has come back clean (one stream
-        // synchronisation, ~20 us against a 15 ms kernel).  Nothing behind this point changes the three words.
-        FA_HIP_TRY(hipMemcpyAsync(&back, a.err, sizeof back, hipMemcpyDeviceToHost, st));  // (the scanner's total: headers and tails included)
-        FA_HIP_TRY(hipStreamSynchronize(st));
-        if (back.err == 1 || (back.err == 0 && back.total > capacity_bytes)) return FA_ERROR_ALLOC;  // the blob does not fit the caller's buffer: nothing else is launched
-        if (back.err) {
-            std::fprintf(stderr, "flacarray_hip: single-pass encode failed (flags %d: 1 = offset outside the buffer, 2 = a frame timed out waiting for its offset, 4 = the scanner timed out)\n", back.err);
-            return FA_ERROR_ENCODE_PROCESS;
-        }
-    }
+    // A frame that was dropped (no offset in time, or an offset outside the buffer) leaves frame_abs / off_pub of
+    // itself -- and, after a scanner time-out, of every frame behind it -- unwritten: the kernels below would
+    // turn those into addresses.  They run only after the error word has come back clean (one stream
+    // synchronisation, ~20 us against a 15 ms kernel): on an error nothing else is launched.  Nothing behind this
+    // point changes the three words.
+    PublishBack back = {0, 0, 0};
+    rc = read_publish_back(a, st, &back);
+    if (rc) return rc;
     if (tails) {
         // every frame has its offset now: move the short frames from their slots (byte-shifted copy + CRC-16, K5)
         uint32_t* tb = reinterpret_cast<uint32_t*>(ws + pl.off_tbytes);
         int64_t* toff = reinterpret_cast<int64_t*>(ws + pl.off_toff);
         int64_t* tzero = reinterpret_cast<int64_t*>(ws + pl.off_tzero);
-        launch_fused_tail_prep(st, a.off_pub, a.frame_bytes, n_stream, pl.nf, a.frame_abs, tb, toff, tzero);
+        launch_fused_tail_prep(st, a.off_pub, a.frame_bytes, n_stream, fp.nf, a.frame_abs, tb, toff, tzero);
         const uint16_t* crc5 = nullptr;
         rc = get_crc_tab(&crc5);
         if (rc) return rc;
@@ -1425,7 +1422,7 @@ static int fused_encode_run(const void* d_data, bool f32, const float* d_quanta,
         if (nblk > 32768) nblk = 32768;
         launch_compact_frames(st, nblk, reinterpret_cast<const uint8_t*>(ws + pl.off_tslots), tb, toff, tzero, 1, n_stream, crc5, d_bytes, kSlotBytes);
     }
-    launch_fused_finish(st, d_bytes, a.frame_abs, a.frame_bytes, n_stream, pl.nf, stream_size, (int32_t)kMaxBlock, (int32_t)pl.tail_bs, 1, pl.hb,
+    launch_fused_finish(st, d_bytes, a.frame_abs, a.frame_bytes, n_stream, fp.nf, stream_size, (int32_t)kMaxBlock, (int32_t)fp.tail_bs, 1, fp.hb,
                         d_starts, d_nbytes, a.total);
     prof_end(3, st);
     // No second wait: the error word, the NaN flag and the total are in hand, and what is still queued (a short-frame
@@ -1441,165 +1438,105 @@ static int fused_encode_run(const void* d_data, bool f32, const float* d_quanta,
 // Small arrays of K3F's geometries take K3G too: K3F's sequence is four launches and two host waits (five more launches
 // when the streams end in a short frame), K3G's is one launch and one wait, which wins until the frames are many enough
 // for K3F's faster frame loop to pay (tools/bench_placed.py).  FLACARRAY_HIP_PLACED_BELOW overrides the frame count.
-static bool placed_preferred(int64_t n_stream, int64_t stream_size) {
+static bool placed_preferred(const FramePlan& fp) {
     // (tools/kb_crossover_placed.py, whole frames: 512 frames 0.089 against 0.096 ms, 1024 frames 0.104 against 0.099, 2048
     // frames 0.144 against 0.115; streams that end in a short frame add five launches to K3F's side: 3000 frames 0.166 against 0.22)
-    int64_t below = (stream_size % kMaxBlock == 0) ? kPlacedBelowFrames / 4 : kPlacedBelowFrames;
+    int64_t below = (fp.tail_bs == kMaxBlock) ? kPlacedBelowFrames / 4 : kPlacedBelowFrames;
     if (const char* e = std::getenv("FLACARRAY_HIP_PLACED_BELOW")) below = std::atoll(e);
-    return n_stream * ((stream_size + kMaxBlock - 1) / kMaxBlock) < below;
+    return fp.F < below;
 }
 
 // the single-pass sequence of every geometry K3F does not take: zero the publish words, K3G, stream headers
-static int placed_encode_run(const int32_t* d_data, int nch, int64_t n_stream, int64_t stream_size, uint32_t level, void* d_workspace,
-                             int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
-                             int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info, void* stream) {
+static int placed_encode_run(const FramePlan& fp, const int32_t* d_data, void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes,
+                             int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info,
+                             void* stream) {
     FA_API_LOCK;
-    PlacedPlan pl;
-    int rc = make_placed_plan(n_stream, stream_size, level, nch, &pl);
-    if (rc) return rc;
-    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
-    if (!d_bytes || capacity_bytes < n_stream * pl.hb + 64) return FA_ERROR_ALLOC;  // (as for K3F: the buffer may gamble, but holds the headers)
+    const PlacedLayout pl = placed_layout(fp);
+    if (!d_workspace || workspace_bytes < single_pass_need(fp)) return FA_ERROR_ALLOC;
+    if (!d_bytes || capacity_bytes < fp.n_stream * fp.hb + 64) return FA_ERROR_ALLOC;  // (as for K3F: the buffer may gamble, but holds the headers)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(d_workspace);
     prof_begin(3, st);
-    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_zero, 0, pl.zero_bytes, st));
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.pub.off_zero, 0, pl.pub.zero_bytes, st));
     EncodeArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.data = d_data; a.n_stream = n_stream; a.stream_size = stream_size; a.nframes = pl.nf;
-    a.B = pl.P.blocksize; a.tail_bs = pl.tail_bs;
-    a.max_lpc_order = pl.P.max_lpc_order; a.max_porder = pl.P.max_porder; a.precision = pl.P.qlp_precision;
-    rc = get_window(a.B, &a.win);
+    int rc = fill_encode_args(fp, d_data, reinterpret_cast<uint8_t*>(ws + pl.off_slots), reinterpret_cast<uint32_t*>(ws + pl.pub.off_fbytes), d_info, &a);
     if (rc) return rc;
-    rc = get_window(a.tail_bs, &a.win_tail);
+    rc = frame_header_table(ds_, fp, st, &a.hdr);
     if (rc) return rc;
-    a.slots = reinterpret_cast<uint8_t*>(ws + pl.off_slots);
-    a.slot_stride = pl.slot_stride;
-    a.frame_bytes = reinterpret_cast<uint32_t*>(ws + pl.off_fbytes);
-    a.info = reinterpret_cast<FrameInfo*>(d_info);
-    a.pmax_full = max_porder_for(a.B, a.max_porder, 0);
-    a.pmax_tail = max_porder_for(a.tail_bs, a.max_porder, 0);
-    a.escale_full = 0.5 / (double)a.B;
-    a.escale_tail = 0.5 / (double)a.tail_bs;
-    {
-        // frame header fields by frame number (as in encode_device_begin: tabulated on the host, cached on the device)
-        void* dp = nullptr;
-        const size_t ntab = (size_t)pl.nf * (nch == 2 ? 2 : 1);
-        rc = get_scratch(9, ntab * sizeof(uint4) + 256, &dp);
-        if (rc) return rc;
-        if (ds_->c_nf != pl.nf || ds_->c_B != a.B || ds_->c_tail != a.tail_bs || ds_->c_nch != nch || ds_->c_dp != dp ||
-            ds_->c_epoch != ds_->scratch_epoch) {
-            ds_->h_hdr.resize(ntab);
-            for (int64_t f = 0; f < pl.nf; ++f) {
-                ds_->h_hdr[(size_t)f] = frame_header_entry((uint64_t)f, (f == pl.nf - 1) ? a.tail_bs : a.B, nch);
-                if (nch == 2) ds_->h_hdr[(size_t)(pl.nf + f)] = frame_header_entry((uint64_t)f, (f == pl.nf - 1) ? a.tail_bs : a.B, nch, true);
-            }
-            FA_HIP_TRY(hipMemcpyAsync(dp, ds_->h_hdr.data(), ntab * sizeof(uint4), hipMemcpyHostToDevice, st));
-            FA_HIP_TRY(hipStreamSynchronize(st));  // h_hdr is reused by the next call
-            ds_->c_nf = pl.nf; ds_->c_B = a.B; ds_->c_tail = a.tail_bs; ds_->c_nch = nch; ds_->c_dp = dp; ds_->c_epoch = ds_->scratch_epoch;
-        }
-        a.hdr = reinterpret_cast<const uint4*>(dp);
-    }
     FusedArgs p;
     std::memset(&p, 0, sizeof p);
-    p.n_stream = n_stream; p.stream_size = stream_size; p.nframes = pl.nf; p.total_frames = pl.F;
-    p.blob = d_bytes; p.capacity = capacity_bytes; p.hb = pl.hb;
-    p.frame_bytes = a.frame_bytes;
-    p.frame_abs = reinterpret_cast<int64_t*>(ws + pl.off_fabs);
+    p.n_stream = fp.n_stream; p.stream_size = fp.stream_size; p.nframes = fp.nf; p.total_frames = fp.F;
+    p.blob = d_bytes; p.capacity = capacity_bytes; p.hb = fp.hb;
+    point_into_publish_block(pl.pub, ws, &p);
     p.info = a.info;
-    p.size_pub = reinterpret_cast<uint32_t*>(ws + pl.off_size);
-    p.off_pub = reinterpret_cast<unsigned long long*>(ws + pl.off_off);
-    // (the scanner's total lands next to the error word, inside the 256 zeroed bytes that hold the ticket: one copy brings both back)
-    p.total = reinterpret_cast<int64_t*>(ws + pl.off_ticket + 16);
-    p.ticket = reinterpret_cast<uint32_t*>(ws + pl.off_ticket);
-    p.err = reinterpret_cast<int*>(ws + pl.off_ticket + 8);
     rc = get_crc_tab(&p.crc_tab);  // (K5's tables: the placement step is K5's per-frame copy)
     if (rc) return rc;
-#ifdef FA_STAMPS
-    {
-        void* sp = nullptr;
-        if (get_scratch(6, 512, &sp) == 0) {
-            if (!ds_->stamps_zeroed) { (void)hipMemset(sp, 0, 512); ds_->stamps_zeroed = true; }
-            p.stamps = reinterpret_cast<unsigned long long*>(sp);
-            a.stamps = p.stamps;  // (the frame body's own phases: stamps[0..16], as in the slot kernel)
-            (void)hipMemsetAsync(p.stamps + 28, 0, 8, st);  // (start time of the call's first workgroup)
-        }
-    }
-#endif
+    p.stamps = a.stamps = stamps_scratch(ds_);  // (the frame body's own phases: stamps[0..16], as in the slot kernel)
+    if (p.stamps) (void)hipMemsetAsync(p.stamps + 28, 0, 8, st);  // (start time of the call's first workgroup)
     p.starts = d_starts;
     p.nbytes = d_nbytes;
     prof_begin(0, st);
-    launch_encode_placed(st, a, p, nch, placed_grid(pl.F));
+    launch_encode_placed(st, a, p, fp.nch, placed_grid(fp.F));
     prof_end(0, st);
     prof_end(3, st);
-    // one wait: the error word and the total (the kernel has written the index and the stream headers itself)
-    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
-    static_assert(sizeof back == 16, "error word at +8, total at +16 of the ticket block");
-    FA_HIP_TRY(hipMemcpyAsync(&back, p.err, sizeof back, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(hipStreamSynchronize(st));
     FA_HIP_TRY(hipGetLastError());
-    const int h_err = back.err;
-    const int64_t h_tot = back.total;
-    if (h_err == 1 || (h_err == 0 && h_tot > capacity_bytes)) return FA_ERROR_ALLOC;  // the blob does not fit the caller's buffer
-    if (h_err) {
-        std::fprintf(stderr, "flacarray_hip: single-pass encode failed (flags %d: 1 = offset outside the buffer, 2 = a frame timed out waiting for its offset, 4 = the scanner timed out)\n", h_err);
-        return FA_ERROR_ENCODE_PROCESS;
-    }
-    *h_total_bytes = h_tot;
+    // one wait: the error word and the total (the kernel has written the index and the stream headers itself)
+    PublishBack back = {0, 0, 0};
+    rc = read_publish_back(p, st, &back);
+    if (rc) return rc;
+    *h_total_bytes = back.total;
     return FA_ERROR_NONE;
+}
+
+// int32 (nch 1) and int64 (nch 2, the two words of a sample as two channels) arrays
+static int encode_device(const int32_t* d_data, int nch, int64_t n_stream, int64_t stream_size, uint32_t level, void* d_workspace,
+                         int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts, int64_t* d_nbytes,
+                         int64_t* h_total_bytes, int32_t* d_info, void* stream) {
+    FramePlan fp;
+    int rc = make_frame_plan(n_stream, stream_size, level, nch, &fp);
+    if (rc) return rc;
+    if (slots_forced()) {  // diagnostic: the slot sequence into the same caller-provided buffer
+        rc = encode_device_begin(d_data, nch, n_stream, stream_size, level, d_workspace, workspace_bytes, d_starts, d_nbytes, h_total_bytes,
+                                 d_info, stream);
+        if (rc) return rc;
+        if (*h_total_bytes > capacity_bytes) return FA_ERROR_ALLOC;
+        return encode_device_finish(nch, n_stream, stream_size, level, d_workspace, d_starts, d_bytes, stream);
+    }
+    // frames K3F does not cover (two channels, short blocks of levels 0-2, streams shorter than two frames, lengths that are
+    // not a multiple of 4, unaligned rows): K3G
+    if (!fused_geometry(fp) || (reinterpret_cast<uintptr_t>(d_data) & 15) || placed_preferred(fp))
+        return placed_encode_run(fp, d_data, d_workspace, workspace_bytes, d_bytes, capacity_bytes, d_starts, d_nbytes, h_total_bytes, d_info,
+                                 stream);
+    return fused_encode_run(fp, d_data, false, nullptr, nullptr, nullptr, d_workspace, workspace_bytes, d_bytes, capacity_bytes, d_starts,
+                            d_nbytes, h_total_bytes, d_info, stream);
 }
 
 int fa_encode_i32_device(const int32_t* d_data, int64_t n_stream, int64_t stream_size, uint32_t level, void* d_workspace,
                          int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
                          int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info, void* stream) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
-    if (slots_forced()) {  // diagnostic: the slot sequence into the same caller-provided buffer
-        int rc = encode_device_begin(d_data, 1, n_stream, stream_size, level, d_workspace, workspace_bytes, d_starts, d_nbytes,
-                                     h_total_bytes, d_info, stream);
-        if (rc) return rc;
-        if (*h_total_bytes > capacity_bytes) return FA_ERROR_ALLOC;
-        return encode_device_finish(1, n_stream, stream_size, level, d_workspace, d_starts, d_bytes, stream);
-    }
-    // frames K3F does not cover (short blocks of levels 0-2, streams shorter than two frames, lengths that are not a multiple
-    // of 4, unaligned rows): K3G
-    if (!fused_geometry(n_stream, stream_size, level) || (reinterpret_cast<uintptr_t>(d_data) & 15) || placed_preferred(n_stream, stream_size))
-        return placed_encode_run(d_data, 1, n_stream, stream_size, level, d_workspace, workspace_bytes, d_bytes, capacity_bytes, d_starts,
-                                 d_nbytes, h_total_bytes, d_info, stream);
-    return fused_encode_run(d_data, false, nullptr, nullptr, nullptr, n_stream, stream_size, level, d_workspace, workspace_bytes, d_bytes,
-                            capacity_bytes, d_starts, d_nbytes, h_total_bytes, d_info, stream);
+    return encode_device(d_data, 1, n_stream, stream_size, level, d_workspace, workspace_bytes, d_bytes, capacity_bytes, d_starts, d_nbytes,
+                         h_total_bytes, d_info, stream);
+}
+
+int fa_encode_i64_device(const int64_t* d_data, int64_t n_stream, int64_t stream_size, uint32_t level, void* d_workspace,
+                         int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
+                         int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info, void* stream) {
+    return encode_device(reinterpret_cast<const int32_t*>(d_data), 2, n_stream, stream_size, level, d_workspace, workspace_bytes, d_bytes,
+                         capacity_bytes, d_starts, d_nbytes, h_total_bytes, d_info, stream);
 }
 
 int fa_encode_f32_device(const float* d_data, int64_t n_stream, int64_t stream_size, uint32_t level, const float* d_quanta,
                          void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes,
                          int64_t* d_starts, int64_t* d_nbytes, float* d_offsets, float* d_gains, int64_t* h_total_bytes,
                          int32_t* d_info, void* stream) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    FramePlan fp;
+    const int rc = make_frame_plan(n_stream, stream_size, level, 1, &fp);
+    if (rc && rc != FA_ERROR_ENCODE_PROCESS) return rc;  // (the argument errors come first; a limit is not K3F's geometry, below)
     if (!d_offsets || !d_gains) return FA_ERROR_CONVERT_TYPE;
     // (other geometries: quantise with fa_float32_to_int32_device, then encode the integers)
-    if (!fused_geometry(n_stream, stream_size, level, true) || (reinterpret_cast<uintptr_t>(d_data) & 15)) return FA_ERROR_ENCODE_INIT;
-    return fused_encode_run(d_data, true, d_quanta, d_offsets, d_gains, n_stream, stream_size, level, d_workspace, workspace_bytes, d_bytes,
-                            capacity_bytes, d_starts, d_nbytes, h_total_bytes, d_info, stream);
-}
-
-int fa_encode_i64_device(const int64_t* d_data, int64_t n_stream, int64_t stream_size, uint32_t level, void* d_workspace,
-                         int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
-                         int64_t* d_nbytes, int64_t* h_total_bytes, int32_t* d_info, void* stream) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
-    const int32_t* d32 = reinterpret_cast<const int32_t*>(d_data);
-    if (slots_forced()) {
-        int rc = encode_device_begin(d32, 2, n_stream, stream_size, level, d_workspace, workspace_bytes, d_starts, d_nbytes, h_total_bytes,
-                                     d_info, stream);
-        if (rc) return rc;
-        if (*h_total_bytes > capacity_bytes) return FA_ERROR_ALLOC;
-        return encode_device_finish(2, n_stream, stream_size, level, d_workspace, d_starts, d_bytes, stream);
-    }
-    return placed_encode_run(d32, 2, n_stream, stream_size, level, d_workspace, workspace_bytes, d_bytes, capacity_bytes, d_starts, d_nbytes,
-                             h_total_bytes, d_info, stream);
+    if (rc || !fused_geometry(fp, true) || (reinterpret_cast<uintptr_t>(d_data) & 15)) return FA_ERROR_ENCODE_INIT;
+    return fused_encode_run(fp, d_data, true, d_quanta, d_offsets, d_gains, d_workspace, workspace_bytes, d_bytes, capacity_bytes, d_starts,
+                            d_nbytes, h_total_bytes, d_info, stream);
 }
 
 // ---- append and overwrite (splice_kernels.hpp, K10): span decode, encode of the patched span image, splice --------------
@@ -1616,14 +1553,25 @@ struct SplicePlan {
     bool append;  // (a negative n_old_bytes is an argument error for overwrite, a stream that does not fit for append)
     size_t off_img, off_stage, off_sub, off_blob, off_idx, off_slot, off_off, off_small, off_ws, total;
 };
+// The old store's block size and frame count, from the frame plan of its geometry; the plan's argument errors are the
+// call's.  (Its limits are not: they were the old store's own encode's to refuse, and the span's encode has its plan below.)
+static int splice_old_geometry(int nch, int64_t n_stream, int64_t stream_size, uint32_t level, SplicePlan* pl) {
+    FramePlan old;
+    const int rc = make_frame_plan(n_stream, stream_size, level, nch, &old);
+    if (rc && rc != FA_ERROR_ENCODE_PROCESS) return rc;
+    pl->B = old.B;
+    pl->nf_old = old.nf;
+    return FA_ERROR_NONE;
+}
 // the rest of a plan whose B, f0, f1, nf_old, lo, hi, len, col and size_new are set
 static int finish_splice_plan(int nch, int64_t n_stream, int64_t m, int64_t n, uint32_t level, SplicePlan* pl) {
-    pl->nf_enc = (pl->len + pl->B - 1) / pl->B;
+    FramePlan enc;  // the encode of the (m, len) image
+    if (make_frame_plan(m, pl->len, level, nch, &enc) != FA_ERROR_NONE) return FA_ERROR_ENCODE_INIT;
+    pl->nf_enc = enc.nf;
     pl->nf_new = pl->f0 + pl->nf_enc + (pl->nf_old - pl->f1);
     pl->exact = (pl->col == 0 && n == pl->len);
-    pl->enc_cap = capacity_bytes_for(m, pl->len, level, nch);
+    pl->enc_cap = enc.capacity;
     pl->enc_ws = single_pass_workspace_for(m, pl->len, level, nch);
-    if (pl->enc_cap < 0 || pl->enc_ws < 0) return FA_ERROR_ENCODE_INIT;
     // the frames behind the span keep their numbers: no suffix, or no change in the frame count
     if (pl->f1 != pl->nf_old && pl->nf_enc != pl->f1 - pl->f0) return FA_ERROR_ENCODE_INIT;
     const size_t elt = 4 * (size_t)nch;
@@ -1643,12 +1591,11 @@ static int finish_splice_plan(int nch, int64_t n_stream, int64_t m, int64_t n, u
     return FA_ERROR_NONE;
 }
 static int make_append_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t n, uint32_t level, SplicePlan* pl) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0 || n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    const int rc = splice_old_geometry(nch, n_stream, stream_size, level, pl);
+    if (rc) return rc;
+    if (n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
     pl->append = true;
-    pl->B = (level <= 2) ? 1152 : 4096;
-    pl->nf_old = pl->f1 = (stream_size + pl->B - 1) / pl->B;
+    pl->f1 = pl->nf_old;
     pl->f0 = stream_size / pl->B;  // the old full frames are kept
     pl->lo = pl->f0 * pl->B;
     pl->hi = stream_size;
@@ -1658,13 +1605,12 @@ static int make_append_plan(int nch, int64_t n_stream, int64_t stream_size, int6
     return finish_splice_plan(nch, n_stream, n_stream, n, level, pl);
 }
 static int make_overwrite_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t n, uint32_t level, SplicePlan* pl) {
-    if (level > 8) return FA_ERROR_INVALID_LEVEL;
-    if (n_stream <= 0 || m <= 0 || m > n_stream) return FA_ERROR_ZERO_NSTREAM;
-    if (stream_size <= 0 || n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+    // (a count of participating streams outside [1, n_stream] is refused where the plan refuses a stream count)
+    const int rc = splice_old_geometry(nch, (m > 0 && m <= n_stream) ? n_stream : 0, stream_size, level, pl);
+    if (rc) return rc;
+    if (n <= 0) return FA_ERROR_ZERO_STREAMSIZE;
     if (first < 0 || first > stream_size || n > stream_size - first) return FA_ERROR_DECODE_SAMPLE_RANGE;
     pl->append = false;
-    pl->B = (level <= 2) ? 1152 : 4096;
-    pl->nf_old = (stream_size + pl->B - 1) / pl->B;
     pl->f0 = first / pl->B;
     pl->f1 = std::min<int64_t>(pl->nf_old, (first + n + pl->B - 1) / pl->B);
     pl->lo = pl->f0 * pl->B;
@@ -2618,8 +2564,8 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     for (int64_t i = 0; i < n_stream; ++i) starts[i] = 0;
     if (n_stream < 0 || stream_size < 0) return FA_ERROR_ZERO_NSTREAM;
     if (fa_device_count() <= 0) return FA_ERROR_DEVICE;
-    EncodePlan one;
-    int rc = make_plan(1, stream_size, level, &one, nch);
+    FramePlan one;  // one stream: frames per stream, and the worst case of a stream
+    int rc = make_frame_plan(1, stream_size, level, nch, &one);
     if (rc) return rc;
     int dev = 0;
     FA_HIP_TRY(hipGetDevice(&dev));
@@ -2630,8 +2576,10 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     // (verifying two-channel chunks also takes the decoder's planar image, as large again as the chunk's input)
     const int64_t chunk = host_chunk_streams(n_stream, stream_bytes * (verifying && nch == 2 ? 2 : 1), 0x7fffffffLL / one.nf, signing);
     const int64_t n_chunks = (n_stream + chunk - 1) / chunk;
-    const bool fused_f32 = f32 && fused_geometry(chunk, stream_size, level, true) &&
-                           (n_stream % chunk == 0 || fused_geometry(n_stream % chunk, stream_size, level, true));
+    // (K3F's float geometries do not depend on the stream count: the last, smaller chunk takes the route of the others)
+    FramePlan per_chunk;
+    if ((rc = make_frame_plan(chunk, stream_size, level, nch, &per_chunk))) return rc;
+    const bool fused_f32 = f32 && fused_geometry(per_chunk, true);
 
     // device buffers: two input slots, output, workspace, per-stream tables
     void *d_in2 = nullptr, *d_ws = nullptr, *d_aux = nullptr, *d_out = nullptr, *d_int = nullptr;
@@ -2653,12 +2601,12 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
     int64_t* d_mm = reinterpret_cast<int64_t*>(d_gain64 + chunk);  // encode verification: first mismatch per stream
     unsigned char* d_dig = reinterpret_cast<unsigned char*>(d_mm + chunk);  // signing: the chunk's digests (16-byte aligned: d_aux is, chunk * 48 is)
     std::vector<int64_t> h_mm(verifying ? (size_t)chunk : 0);
-    const int64_t cap_chunk = capacity_bytes_for(chunk, stream_size, level, nch);
+    const int64_t cap_chunk = per_chunk.capacity;
     if ((rc = get_scratch(3, (size_t)cap_chunk + 256, &d_out))) return rc;
     if (((f32 && !fused_f32) || f64) && (rc = get_scratch(11, in_b + 256, &d_int))) return rc;
 
     // the blob: worst case reserved (address space only), populated ahead of the copies, trimmed at the end
-    const int64_t cap_total = n_stream * one.nf * (int64_t)kSlotBytes * nch + n_stream * stream_header_bytes(one.nf) + 64;
+    const int64_t cap_total = n_stream * one.capacity + 64;
     unsigned char* blob = reinterpret_cast<unsigned char*>(std::malloc((size_t)cap_total));
     bool reserved = (blob != nullptr);
     if (!reserved) {  // no overcommit: fall back to growing the blob chunk by chunk
@@ -2756,7 +2704,9 @@ static int encode_host(const void* data_v, int nch, int64_t n_stream, int64_t st
             if (err) break;
         }
         if (n_chunks > 1) {
-            // the kernels are done with the input slot (the encode calls end with a stream synchronisation)
+            // The kernels are done with the input slot.  K3G and the slot sequence end with a stream synchronisation; K3F
+            // returns with its finish kernels still queued, but those read the workspace and the blob only: K3F itself
+            // and the short frames' encoder, the readers of the input, ran before its one wait.
             feed.done_with(c);
         }
         if ((size_t)(running + total) > blob_cap) {  // (only without the reservation)

@@ -183,6 +183,30 @@ def wrap_int64_to_float64(idata, n_stream, stream_size, offsets, gains):
     return wrap_int32_to_float32(idata, n_stream, stream_size, offsets, gains, _f64=True)
 
 
+class _EncodeSetting:
+    """Hold one of the library's process-wide encode settings (fa_set_encode_verify, fa_set_encode_md5) at `value` for one
+    host encode call (None: the default as it is).  The setting's Python lock covers set, call and restore; the library
+    serialises host encodes anyway."""
+
+    setter = None  # name of the C setter
+    lock = None
+
+    def __init__(self, value):
+        self.value = value
+
+    def __enter__(self):
+        if self.value is not None:
+            self.lock.acquire()
+            self.prev = getattr(_lib.lib(), self.setter)(1 if self.value else 0)
+        return self
+
+    def __exit__(self, *exc):
+        if self.value is not None:
+            getattr(_lib.lib(), self.setter)(self.prev)
+            self.lock.release()
+        return False
+
+
 _encode_verify_lock = threading.Lock()
 
 
@@ -201,24 +225,10 @@ def _encode_verify_default():
     return bool(_lib.lib().fa_set_encode_verify(-1))
 
 
-class _EncodeVerify:
-    """Hold the library's encode-verify setting at `verify` for one host encode call (None: the default as it is).  One
-    Python lock covers set, call and restore; the library serialises host encodes anyway."""
+class _EncodeVerify(_EncodeSetting):
+    """The encode-verify setting, held for one host encode call."""
 
-    def __init__(self, verify):
-        self.verify = verify
-
-    def __enter__(self):
-        if self.verify is not None:
-            _encode_verify_lock.acquire()
-            self.prev = _lib.lib().fa_set_encode_verify(1 if self.verify else 0)
-        return self
-
-    def __exit__(self, *exc):
-        if self.verify is not None:
-            _lib.lib().fa_set_encode_verify(self.prev)
-            _encode_verify_lock.release()
-        return False
+    setter, lock = "fa_set_encode_verify", _encode_verify_lock
 
 
 _encode_md5_lock = threading.Lock()
@@ -239,24 +249,10 @@ def _encode_md5_default():
     return bool(_lib.lib().fa_set_encode_md5(-1))
 
 
-class _EncodeMd5:
-    """Hold the library's encode-md5 setting at `md5` for one host encode call (None: the default as it is); the twin
-    of _EncodeVerify, always entered after it."""
+class _EncodeMd5(_EncodeSetting):
+    """The encode-md5 setting, held for one host encode call; always entered after _EncodeVerify."""
 
-    def __init__(self, md5):
-        self.md5 = md5
-
-    def __enter__(self):
-        if self.md5 is not None:
-            _encode_md5_lock.acquire()
-            self.prev = _lib.lib().fa_set_encode_md5(1 if self.md5 else 0)
-        return self
-
-    def __exit__(self, *exc):
-        if self.md5 is not None:
-            _lib.lib().fa_set_encode_md5(self.prev)
-            _encode_md5_lock.release()
-        return False
+    setter, lock = "fa_set_encode_md5", _encode_md5_lock
 
 
 def _check_encode(errcode):
@@ -283,14 +279,11 @@ def _wrap_encode(fn, flatdata, n_stream, stream_size, level, dtype=np.int32):
     return (_adopt_malloc(raw.value, n_bytes.value), flat_starts, flat_nbytes)
 
 
-def encode_flac_f32(data, quanta, level):
-    """float32 array -> (compressed, starts, nbytes, offsets, gains) in one trip over PCIe (fa_encode_f32_host): the
-    samples go up once and are quantised where the encoder loads them -- the same integers, offsets, gains and bytes as
-    `float_to_int` (utils.py:246-342) followed by `encode_flac` (libflacarray.pyx:529-594), which moves the array up,
-    the integers down, and the integers up again.  `quanta`: None (from each stream's range) or one value per stream."""
+def _encode_flac_float(data, quanta, level, ft, fn):
+    """The body of encode_flac_f32 / encode_flac_f64: `ft` the numpy float type, `fn` the library's host entry point."""
     _lib.require_device()
-    if data.dtype != np.dtype(np.float32):
-        raise ValueError("Only float32 data is supported")
+    if data.dtype != np.dtype(ft):
+        raise ValueError(f"Only {np.dtype(ft).name} data is supported")
     if level < 0 or level > 8:
         raise RuntimeError("FLAC only supports compression levels 0-8")
     data = np.ascontiguousarray(data)
@@ -299,22 +292,30 @@ def encode_flac_f32(data, quanta, level):
     n_stream = int(np.prod(lead))
     q = None
     if quanta is not None:
-        q = np.ascontiguousarray(quanta, dtype=np.float32).reshape(-1)
+        q = np.ascontiguousarray(quanta, dtype=ft).reshape(-1)
         if q.size != n_stream:
             raise ValueError("quanta must have one value per stream")
     flat_starts = np.empty(n_stream, dtype=np.int64)
     flat_nbytes = np.empty(n_stream, dtype=np.int64)
-    offsets = np.empty(n_stream, dtype=np.float32)
-    gains = np.empty(n_stream, dtype=np.float32)
+    offsets = np.empty(n_stream, dtype=ft)
+    gains = np.empty(n_stream, dtype=ft)
     n_bytes = ctypes.c_int64(0)
     raw = ctypes.c_void_p(None)
-    errcode = _lib.lib().fa_encode_f32_host(_ptr(data), n_stream, stream_size, level, _ptr(q) if q is not None else None,
-                                            ctypes.byref(n_bytes), _ptr(flat_starts), ctypes.byref(raw), _ptr(offsets), _ptr(gains))
+    errcode = fn(_ptr(data), n_stream, stream_size, level, _ptr(q) if q is not None else None, ctypes.byref(n_bytes), _ptr(flat_starts),
+                 ctypes.byref(raw), _ptr(offsets), _ptr(gains))
     _check_encode(errcode)
     flat_nbytes[:-1] = np.diff(flat_starts)
     flat_nbytes[-1] = n_bytes.value - flat_starts[-1]
     return (_adopt_malloc(raw.value, n_bytes.value), flat_starts.reshape(lead), flat_nbytes.reshape(lead), offsets.reshape(lead),
             gains.reshape(lead))
+
+
+def encode_flac_f32(data, quanta, level):
+    """float32 array -> (compressed, starts, nbytes, offsets, gains) in one trip over PCIe (fa_encode_f32_host): the
+    samples go up once and are quantised where the encoder loads them -- the same integers, offsets, gains and bytes as
+    `float_to_int` (utils.py:246-342) followed by `encode_flac` (libflacarray.pyx:529-594), which moves the array up,
+    the integers down, and the integers up again.  `quanta`: None (from each stream's range) or one value per stream."""
+    return _encode_flac_float(data, quanta, level, np.float32, _lib.lib().fa_encode_f32_host)
 
 
 def encode_flac_f64(data, quanta, level):
@@ -322,33 +323,7 @@ def encode_flac_f64(data, quanta, level):
     float64 samples go up once, are quantised on the device (float64_to_int64, utils.c:245-327) and encoded from there as
     two-channel streams -- the same integers, offsets, gains and bytes as `float_to_int` followed by `encode_flac`
     (compress.py:50-84), which moves the array up, the int64 image down, and the int64 image up again."""
-    _lib.require_device()
-    if data.dtype != np.dtype(np.float64):
-        raise ValueError("Only float64 data is supported")
-    if level < 0 or level > 8:
-        raise RuntimeError("FLAC only supports compression levels 0-8")
-    data = np.ascontiguousarray(data)
-    stream_size = data.shape[-1]
-    lead = data.shape[:-1] if data.ndim > 1 else (1,)
-    n_stream = int(np.prod(lead))
-    q = None
-    if quanta is not None:
-        q = np.ascontiguousarray(quanta, dtype=np.float64).reshape(-1)
-        if q.size != n_stream:
-            raise ValueError("quanta must have one value per stream")
-    flat_starts = np.empty(n_stream, dtype=np.int64)
-    flat_nbytes = np.empty(n_stream, dtype=np.int64)
-    offsets = np.empty(n_stream, dtype=np.float64)
-    gains = np.empty(n_stream, dtype=np.float64)
-    n_bytes = ctypes.c_int64(0)
-    raw = ctypes.c_void_p(None)
-    errcode = _lib.lib().fa_encode_f64_host(_ptr(data), n_stream, stream_size, level, _ptr(q) if q is not None else None,
-                                            ctypes.byref(n_bytes), _ptr(flat_starts), ctypes.byref(raw), _ptr(offsets), _ptr(gains))
-    _check_encode(errcode)
-    flat_nbytes[:-1] = np.diff(flat_starts)
-    flat_nbytes[-1] = n_bytes.value - flat_starts[-1]
-    return (_adopt_malloc(raw.value, n_bytes.value), flat_starts.reshape(lead), flat_nbytes.reshape(lead), offsets.reshape(lead),
-            gains.reshape(lead))
+    return _encode_flac_float(data, quanta, level, np.float64, _lib.lib().fa_encode_f64_host)
 
 
 def wrap_encode_i32(flatdata, n_stream, stream_size, level):
@@ -663,7 +638,7 @@ def _encode_flac_device(data, level, workspace, return_info, compact, capacity_b
         nf = (stream_size + bs - 1) // bs
         info = torch.zeros((n_stream * nf * (2 if i64 else 1), 8), dtype=torch.int32, device=data.device)
     total = ctypes.c_int64(0)
-    if L.fa_encode_single_pass_supported(n_stream, stream_size, level) and hasattr(L, "fa_encode_i64_device"):
+    if L.fa_encode_single_pass_supported(n_stream, stream_size, level):
         cap = (L.fa_encode_capacity_bytes_i64 if i64 else L.fa_encode_capacity_bytes)(n_stream, stream_size, level)
         if capacity_bytes is not None:
             cap = min(cap, int(capacity_bytes))
@@ -679,27 +654,24 @@ def _encode_flac_device(data, level, workspace, return_info, compact, capacity_b
         compressed = buf[: total.value]
         if compact:
             compressed = compressed.clone()
-        out = (compressed, starts.reshape(starts_shape), nbytes.reshape(starts_shape))
-        return out + (info,) if return_info else out
-    ws_bytes = (L.fa_encode_workspace_bytes_i64 if i64 else L.fa_encode_workspace_bytes)(n_stream, stream_size, level)
-    if ws_bytes < 0:
-        raise RuntimeError("Encoding failed, return code = 512")
-    ws = workspace.get(ws_bytes, data.device)
-    with _on_device(data.device):
-        errcode = (L.fa_encode_i64_device_begin if i64 else L.fa_encode_i32_device_begin)(
-            _dp(data), n_stream, stream_size, level, _dp(ws), ws.numel(), _dp(starts), _dp(nbytes), ctypes.byref(total),
-            _dp(info), _stream_ptr(),
-        )
-        if errcode != 0:
-            raise RuntimeError(f"Encoding failed, return code = {errcode}")
-        compressed = torch.empty(total.value, dtype=torch.uint8, device=data.device)
-        errcode = (L.fa_encode_i64_device_finish if i64 else L.fa_encode_i32_device_finish)(n_stream, stream_size, level, _dp(ws), _dp(starts), _dp(compressed), _stream_ptr())
-        if errcode != 0:
-            raise RuntimeError(f"Encoding failed, return code = {errcode}")
+    else:
+        ws_bytes = (L.fa_encode_workspace_bytes_i64 if i64 else L.fa_encode_workspace_bytes)(n_stream, stream_size, level)
+        if ws_bytes < 0:
+            raise RuntimeError("Encoding failed, return code = 512")
+        ws = workspace.get(ws_bytes, data.device)
+        with _on_device(data.device):
+            errcode = (L.fa_encode_i64_device_begin if i64 else L.fa_encode_i32_device_begin)(
+                _dp(data), n_stream, stream_size, level, _dp(ws), ws.numel(), _dp(starts), _dp(nbytes), ctypes.byref(total),
+                _dp(info), _stream_ptr(),
+            )
+            if errcode != 0:
+                raise RuntimeError(f"Encoding failed, return code = {errcode}")
+            compressed = torch.empty(total.value, dtype=torch.uint8, device=data.device)
+            errcode = (L.fa_encode_i64_device_finish if i64 else L.fa_encode_i32_device_finish)(n_stream, stream_size, level, _dp(ws), _dp(starts), _dp(compressed), _stream_ptr())
+            if errcode != 0:
+                raise RuntimeError(f"Encoding failed, return code = {errcode}")
     out = (compressed, starts.reshape(starts_shape), nbytes.reshape(starts_shape))
-    if return_info:
-        return out + (info,)
-    return out
+    return out + (info,) if return_info else out
 
 
 def set_decode_verify(on):

@@ -261,6 +261,96 @@ def test_c_slot_sequence_on_poisoned_buffers(torch, oracle, L, name, poison):
     assert np.array_equal(d_info.cpu().numpy(), want_info)
 
 
+FA_ERROR_ALLOC, FA_ERROR_ENCODE_INIT, FA_ERROR_CONVERT_TYPE = 1 << 0, 1 << 8, 1 << 19  # include/flacarray_hip.h
+# refusal -> the entry points it applies to ("single": fa_encode_i32 / _i64 / _f32_device, "begin": fa_encode_*_device_begin)
+REFUSALS = {
+    "workspace_one_byte_short": ("single", "begin"),
+    "null_workspace": ("single", "begin"),
+    "null_bytes": ("single",),
+    "capacity_below_headers": ("single",),
+}
+
+
+def _refused_call(torch, L, entry, kind, ns, n, level, refusal):
+    """One call of `entry` on the geometry with one argument made bad; returns (return code, the poisoned buffers with the
+    byte each was filled with).  Everything the call could write is there, full size, so a call that is NOT refused writes
+    into memory that is its to write."""
+    wide = kind in ("i64", "f64")
+    sfx = "_i64" if wide else ""
+    dt = {"i32": torch.int32, "i64": torch.int64, "f32": torch.float32, "f64": torch.int64}[kind]
+    xd = torch.zeros((ns, n), dtype=dt, device="cuda")
+    nf = -(-n // (1152 if level <= 2 else 4096))
+    need = int(getattr(L, ("fa_encode_workspace_bytes" if entry == "begin" else "fa_encode_single_pass_workspace_bytes") + sfx)(ns, n, level))
+    cap = int(getattr(L, "fa_encode_capacity_bytes" + sfx)(ns, n, level))
+    assert need > 0 and cap > 0
+    fill = lambda nbytes, v: torch.full((nbytes,), v, dtype=torch.uint8, device="cuda")  # noqa: E731
+    ws, buf = fill(need, 0x5A), fill(cap, 0xA5)
+    d_st, d_nb, d_info = fill(ns * 8, 0xC3), fill(ns * 8, 0xC3), fill(ns * nf * (2 if wide else 1) * 32, 0xC3)
+    d_off, d_gain = fill(ns * 4, 0x3C), fill(ns * 4, 0x3C)
+    ws_arg, ws_bytes, buf_arg, cap_arg, off_arg = _vp(ws), need, _vp(buf), cap, _vp(d_off)
+    if refusal == "workspace_one_byte_short":
+        ws_bytes = need - 1
+    elif refusal == "null_workspace":
+        ws_arg = None
+    elif refusal == "null_bytes":
+        buf_arg = None
+    elif refusal == "capacity_below_headers":
+        cap_arg = ns * (46 + 18 * nf) + 63  # the stream headers (fLaC, STREAMINFO, SEEKTABLE of nf points) + 64 is the least
+    elif refusal == "null_offsets":
+        off_arg = None
+    else:
+        assert refusal == "not_a_float_geometry"
+    total = ctypes.c_int64(-7)
+    if entry == "begin":
+        rc = getattr(L, f"fa_encode_{'i64' if wide else 'i32'}_device_begin")(_vp(xd), ns, n, level, ws_arg, ws_bytes, _vp(d_st), _vp(d_nb),
+                                                                            ctypes.byref(total), _vp(d_info), None)
+    elif kind == "f32":
+        rc = L.fa_encode_f32_device(_vp(xd), ns, n, level, None, ws_arg, ws_bytes, buf_arg, cap_arg, _vp(d_st), _vp(d_nb), off_arg, _vp(d_gain),
+                                    ctypes.byref(total), _vp(d_info), None)
+    else:
+        rc = getattr(L, f"fa_encode_{'i64' if wide else 'i32'}_device")(_vp(xd), ns, n, level, ws_arg, ws_bytes, buf_arg, cap_arg, _vp(d_st), _vp(d_nb),
+                                                                      ctypes.byref(total), _vp(d_info), None)
+    torch.cuda.synchronize()
+    assert total.value == -7, "a refused call wrote its total"
+    return rc, [(ws, 0x5A), (buf, 0xA5), (d_st, 0xC3), (d_nb, 0xC3), (d_info, 0xC3), (d_off, 0x3C), (d_gain, 0x3C)]
+
+
+def _assert_untouched(buffers, what):
+    for k, (t, v) in enumerate(buffers):
+        assert bool((t == v).all()), f"{what}: buffer {k} (workspace, output, starts, nbytes, info, offsets, gains) was written"
+
+
+@pytest.mark.parametrize("refusal", sorted(REFUSALS))
+@pytest.mark.parametrize("name", MAIN)
+def test_refused_before_launch(torch, L, name, refusal):
+    """The argument checks in front of every encode sequence, on the MAIN routes' shapes and the dispatch of a caller that
+    sets nothing: a workspace one byte short of what the query asks, no workspace, no output buffer, or a capacity one
+    byte short of the stream headers + 64 is FA_ERROR_ALLOC -- from the single-pass entry point of the shape's type
+    (fa_encode_i32_device, _i64_device: the f64 route encodes int64, _f32_device) and from fa_encode_*_device_begin (with
+    its own workspace query; it takes no output buffer) -- and nothing is enqueued: the poisoned output, index, info and
+    workspace buffers hold their poison, *h_total_bytes is not written."""
+    kind, ns, n, level, _ = ROUTES[name]
+    for entry in REFUSALS[refusal]:
+        if entry == "begin" and kind == "f32":
+            continue  # (float32 input has no slot sequence of its own)
+        rc, buffers = _refused_call(torch, L, entry, kind, ns, n, level, refusal)
+        assert rc == FA_ERROR_ALLOC, f"{name} {entry} {refusal}: return code {rc}"
+        _assert_untouched(buffers, f"{name} {entry} {refusal}")
+
+
+def test_refused_f32_before_launch(torch, L):
+    """fa_encode_f32_device without offsets is FA_ERROR_CONVERT_TYPE; at (8, 9192), streams that end in a short frame -- not a
+    geometry K3F quantises in -- FA_ERROR_ENCODE_INIT (with every other argument good: a workspace and a buffer of the
+    queried sizes).  Nothing is written in either case."""
+    kind, ns, n, level, _ = ROUTES["f32_fused"]
+    rc, buffers = _refused_call(torch, L, "single", "f32", ns, n, level, "null_offsets")
+    assert rc == FA_ERROR_CONVERT_TYPE
+    _assert_untouched(buffers, "f32 without offsets")
+    rc, buffers = _refused_call(torch, L, "single", "f32", 8, 9192, 5, "not_a_float_geometry")
+    assert rc == FA_ERROR_ENCODE_INIT
+    _assert_untouched(buffers, "f32 at (8, 9192)")
+
+
 @pytest.mark.parametrize("poison", ["zeros", "ones", "a5"])
 @pytest.mark.parametrize("op", ["append", "overwrite", "overwrite_streams"])
 @pytest.mark.parametrize("wide", [False, True], ids=["i32", "i64"])
