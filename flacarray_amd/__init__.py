@@ -16,6 +16,7 @@ from .libflacarray import (
     compare_flac_device,
     decode_flac,
     decode_flac_device,
+    decode_flac_salvage_device,
     decode_slices_device,
     encode_flac,
     encode_flac_device,
@@ -23,6 +24,7 @@ from .libflacarray import (
     encode_flac_device_f64,
     float32_to_int32_device,
     float64_to_int64_device,
+    frame_status_device,
     md5_device,
     overwrite_flac_device,
     reduce_flac_device,
@@ -32,6 +34,7 @@ from .libflacarray import (
     sign_streams_device,
     std_device,
 )
+from .scrub import FRAME_CRC16, FRAME_HEADER, FRAME_OK, FRAME_UNLOCATED, damaged_ranges
 from .utils import float_to_int, int_to_float, keep_select, stream_md5
 
 array_encode = array_compress
@@ -57,6 +60,13 @@ __all__ = [
     "encode_flac_device_f64",
     "decode_flac_device",
     "decode_slices_device",
+    "frame_status_device",
+    "decode_flac_salvage_device",
+    "damaged_ranges",
+    "FRAME_OK",
+    "FRAME_UNLOCATED",
+    "FRAME_HEADER",
+    "FRAME_CRC16",
     "compare_flac_device",
     "reduce_flac_device",
     "md5_device",

@@ -74,6 +74,10 @@ SYMBOLS = [
     "fa_reduce_i32_device",
     "fa_reduce_i64_device",
     "fa_reduce_indexed",
+    "fa_frame_status_device",
+    "fa_fill_ranges_device",
+    "fa_decode_salvage_i32_device",
+    "fa_decode_salvage_i64_device",
     "fa_encode_f32_host",
     "fa_encode_f64_host",
     "fa_decode_f32_host",
@@ -233,6 +237,13 @@ def lib():
     L.fa_reduce_i64_device.restype = cint
     L.fa_reduce_indexed.argtypes = [vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, cint]
     L.fa_reduce_indexed.restype = cint
+    L.fa_frame_status_device.argtypes = [vp, i64, vp, vp, i64, i64, cint, i64, vp, vp]
+    L.fa_frame_status_device.restype = cint
+    L.fa_fill_ranges_device.argtypes = [vp, cint, i64, vp, vp, vp, vp]
+    L.fa_fill_ranges_device.restype = cint
+    for name in ("fa_decode_salvage_i32_device", "fa_decode_salvage_i64_device"):
+        getattr(L, name).argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp]
+        getattr(L, name).restype = cint
     L.fa_set_encode_md5.argtypes = [cint]
     L.fa_set_encode_md5.restype = cint
     L.fa_profile_enable.argtypes = [cint]

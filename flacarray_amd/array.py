@@ -687,6 +687,54 @@ class FlacArray:
         ft = np.float64 if self._is_int64 else np.float32
         return out + (up(self._stream_offsets, ft), up(self._stream_gains, ft)) if scale else out
 
+    # ---- damage map and decode through errors (addition to the reference API) ----
+    def _block_size(self):
+        """The block size the store was written with: the most common one of its readable STREAMINFO blocks (host)."""
+        from .scrub import store_block_size
+
+        return store_block_size(self._compressed, self._stream_starts, self._stream_nbytes)
+
+    def frame_status(self):
+        """The damage map of the store as it is held: numpy uint8 of shape leading_shape + (nf,), one status per
+        (stream, frame) -- 0 = decodable, FRAME_UNLOCATED, or FRAME_HEADER | FRAME_CRC16 bits (flacarray_amd.scrub).
+        Computed on the device from the resident store (or an upload), never through the decode index, and never
+        raises for damage.  As strong as CRC-16: check_md5() is the stronger check, per stream."""
+        from .libflacarray import frame_status_device
+
+        _, comp, st, nb, _, _ = self._device_store(scale=True)
+        status = frame_status_device(comp, st, nb, self._stream_size, is_int64=self._is_int64, block_size=self._block_size())
+        return status.cpu().numpy().reshape(tuple(self._leading_shape) + (-1,))
+
+    def salvage(self, stream_slice=None, fill=None):
+        """Decode through errors: (array, status).  `array` is shaped as to_array(stream_slice=...) shapes it (same
+        step-1 slice rules): every frame whose status is 0 decoded exactly, the samples of every other frame set to
+        `fill` (None: 0 for an integer store, NaN for a float store); `status` is frame_status() of the whole store."""
+        from .libflacarray import decode_flac_salvage_device
+
+        lo, hi = -1, -1
+        if stream_slice is not None:
+            if stream_slice.step not in (None, 1):
+                raise RuntimeError("Only stream slices with a step size of 1 are supported")
+            lo, hi = stream_slice.indices(self._stream_size)[:2]
+            if hi <= lo:
+                raise RuntimeError("first_sample is larger than last_sample")
+        _, comp, st, nb, off, gain = self._device_store(scale=True)
+        out, status = decode_flac_salvage_device(comp, st, nb, self._stream_size, lo, hi, offsets=off, gains=gain, is_int64=self._is_int64,
+                                                 fill=fill, block_size=self._block_size())
+        arr = out.cpu().numpy()
+        arr = arr.reshape(-1) if self._flatten_single else arr.reshape(self._shape[:-1] + (arr.shape[-1],))
+        return arr, status.cpu().numpy().reshape(tuple(self._leading_shape) + (-1,))
+
+    def damaged_ranges(self, status=None):
+        """The sample ranges `status` (default: frame_status()) fences off: int64 [k, 3], rows (flat stream, first,
+        last) with `last` exclusive, adjacent damaged frames of a stream merged, sorted by (stream, first).  With a
+        status given this is a pure host function."""
+        from .scrub import damaged_ranges
+
+        if status is None:
+            status = self.frame_status()
+        return damaged_ranges(status, self._block_size(), self._stream_size)
+
     @property
     def md5(self):
         """The STREAMINFO MD5 signature of every stream as stored: uint8, leading shape + (16,); all zero = unsigned."""

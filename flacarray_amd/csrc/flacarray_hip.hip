@@ -40,6 +40,7 @@
 #include "splice_kernels.hpp"
 #include "md5_kernels.hpp"
 #include "reduce_kernels.hpp"
+#include "scrub_kernels.hpp"
 
 namespace {
 
@@ -58,7 +59,7 @@ using namespace fa;
 // device share its cached scratch buffers); calls that target different devices -- one process driving several
 // GPUs from several threads -- do not serialise each other.  g_mu guards the map of device states only.
 constexpr int kProfPairs = 6;
-constexpr int kScratchSlots = 17;
+constexpr int kScratchSlots = 22;
 struct DeviceState {
     std::recursive_mutex api_mu;
     std::map<int, float*> windows;  // blocksize -> device tukey(0.5) table
@@ -66,7 +67,9 @@ struct DeviceState {
     uint16_t* crc_tab_fused = nullptr;
     // [10]: K1a partial ranges; [12]: std chunk sums and means, [13]: std summation plans (fa_stream_std_*_device);
     // [14]: the MD5 check's decoded column chunk, [15]: its chaining states, digests and flags (fa_check_md5_device);
-    // [16]: the binned reduction's decoded column chunk (fa_reduce_*)
+    // [16]: the binned reduction's decoded column chunk (fa_reduce_*);
+    // [17]: the damage map's realigned blob, [18]: its tolerant stream table, flags and error block, [19]: its tolerant frame
+    // table, [20]: the salvage decode's task table, [21]: its fill ranges (fa_frame_status_device, fa_decode_salvage_*)
     void* scratch[kScratchSlots] = {};
     size_t scratch_bytes[kScratchSlots] = {};
     uint64_t scratch_epoch = 1;  // bumped whenever a scratch slot is (re)allocated or released: cached contents are then stale
@@ -1770,6 +1773,15 @@ static int overwrite_run(int nch, const unsigned char* d_old, int64_t n_old_byte
 }
 
 }  // extern "C" (a template needs C++ linkage)
+// fill_ranges_kernel<T> (scrub_kernels.hpp) with the element at fill_value
+template <typename T>
+static void launch_fill(void* d_out, int64_t n_ranges, const int64_t* d_off, const int64_t* d_count, const void* fill_value, hipStream_t st) {
+    T v;
+    std::memcpy(&v, fill_value, sizeof(T));
+    const unsigned grid = (unsigned)(n_ranges < (int64_t)1 << 20 ? n_ranges : (int64_t)1 << 20);
+    hipLaunchKernelGGL((fill_ranges_kernel<T>), dim3(grid), dim3(256), 0, st, reinterpret_cast<T*>(d_out), n_ranges, d_off, d_count, v);
+}
+
 template <typename F, typename I>
 static int quantise_given_run(const F* d_in, int64_t n_stream, int64_t n, const F* d_offsets, const F* d_gains, I* d_out, int64_t out_stride,
                               void* stream) {
@@ -2327,6 +2339,181 @@ int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, i
     if (!ix) return FA_ERROR_DECODE_INIT;
     return reduce_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, width, n_sel, d_sel_streams, max_temp_bytes, d_min, d_max,
                          d_sum, d_sq_hi, d_sq_lo, stream, verify);
+}
+
+// ---- damage map and salvage decode (scrub_kernels.hpp) ----
+// What the status pass leaves behind for a decode through it: the (realigned) blob and the tolerant tables.
+struct ScrubTables {
+    const unsigned char* bytes = nullptr;
+    StreamMeta* meta = nullptr;
+    int64_t* ftab = nullptr;
+    int* err = nullptr;  // 64 ints, cleared: the decode's error block
+    int64_t nf = 0;
+};
+
+// The status pass over the whole store, queued on `st` (not waited for).  Non-zero for bad arguments and HIP failures only.
+static int scrub_run(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                     int64_t stream_size, int channels, int64_t block_size, unsigned char* d_status, hipStream_t st, ScrubTables* tb) {
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
+    if (channels != 1 && channels != 2) return FA_ERROR_CONVERT_TYPE;
+    if (block_size < 1 || block_size > 65535) return FA_ERROR_DECODE_INIT;
+    if (n_bytes < 0 || !d_starts || !d_nbytes || !d_status || (n_bytes > 0 && !d_bytes)) return FA_ERROR_DECODE_INIT;
+    const int32_t B = (int32_t)block_size;
+    const int64_t nf = (stream_size + B - 1) / B;
+    if (nf > (int64_t)0x7fffffff * 4 / n_stream) return FA_ERROR_DECODE_SAMPLE_RANGE;  // one wavefront per frame, four per workgroup
+    const int64_t nt = n_stream * nf;
+    // 16-byte loads of the decoders are issued relative to the blob base: realign as they do
+    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) {
+        void* al = nullptr;
+        int rc0 = get_scratch(17, (size_t)n_bytes + 256, &al);
+        if (rc0) return rc0;
+        FA_HIP_TRY(hipMemcpyAsync(al, d_bytes, (size_t)n_bytes, hipMemcpyDeviceToDevice, st));
+        d_bytes = reinterpret_cast<const unsigned char*>(al);
+    }
+    const size_t meta_bytes = align_up((size_t)n_stream * sizeof(StreamMeta), 256);
+    const size_t flag_bytes = align_up((size_t)n_stream, 256);
+    void *p = nullptr, *pt = nullptr;
+    int rc = get_scratch(18, meta_bytes + flag_bytes + 256, &p);
+    if (rc) return rc;
+    if ((rc = get_scratch(19, (size_t)nt * 8 + 256, &pt))) return rc;
+    const uint16_t* tab = nullptr;
+    if ((rc = get_crc_tab_fused(&tab))) return rc;
+    StreamMeta* d_meta = reinterpret_cast<StreamMeta*>(p);
+    uint8_t* d_located = reinterpret_cast<uint8_t*>(p) + meta_bytes;
+    int* d_err = reinterpret_cast<int*>(reinterpret_cast<char*>(p) + meta_bytes + flag_bytes);
+    int64_t* d_ftab = reinterpret_cast<int64_t*>(pt);
+    FA_HIP_TRY(hipMemsetAsync(d_err, 0, 256, st));
+    hipLaunchKernelGGL(scrub_streams_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, d_bytes, d_starts, d_nbytes, n_stream, nf,
+                       n_bytes, B, (int32_t)channels, d_meta, d_located);
+    hipLaunchKernelGGL(scrub_table_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_bytes, d_meta, d_located, n_stream, nf, B, d_ftab);
+    hipLaunchKernelGGL(frame_status_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, d_bytes, n_bytes, d_meta, d_ftab, n_stream, nf, B,
+                       stream_size, (int32_t)channels, tab, d_status);
+    FA_HIP_TRY(hipGetLastError());
+    if (tb) { tb->bytes = d_bytes; tb->meta = d_meta; tb->ftab = d_ftab; tb->err = d_err; tb->nf = nf; }
+    return FA_ERROR_NONE;
+}
+
+int fa_frame_status_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                           int64_t stream_size, int channels, int64_t block_size, unsigned char* d_status, void* stream) {
+    FA_API_LOCK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int rc = scrub_run(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, channels, block_size, d_status, st, nullptr);
+    if (rc) return rc;
+    FA_HIP_TRY(hipStreamSynchronize(st));  // (the tables are cached scratch: the next call may be on another stream)
+    return FA_ERROR_NONE;
+}
+
+int fa_fill_ranges_device(void* d_out, int elem_bytes, int64_t n_ranges, const int64_t* d_off, const int64_t* d_count, const void* fill_value,
+                          void* stream) {
+    FA_API_LOCK;
+    if (elem_bytes != 4 && elem_bytes != 8) return FA_ERROR_CONVERT_TYPE;
+    if (n_ranges < 0 || !fill_value) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    if (n_ranges == 0) return FA_ERROR_NONE;
+    if (!d_out || !d_off || !d_count) return FA_ERROR_DECODE_INIT;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (elem_bytes == 4) launch_fill<int32_t>(d_out, n_ranges, d_off, d_count, fill_value, st);
+    else launch_fill<int64_t>(d_out, n_ranges, d_off, d_count, fill_value, st);
+    FA_HIP_TRY(hipGetLastError());
+    return FA_ERROR_NONE;
+}
+
+// Decode through errors: the status pass, then every frame of status 0 that touches the range through K7 / K7L and the
+// fill value over the samples of every other one.  Exactly one of out_int / out_float is set.
+static int salvage_run(int nch, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                       int64_t stream_size, int64_t first_sample, int64_t last_sample, void* out_int, void* out_float, const void* d_offsets,
+                       const void* d_gains, int64_t block_size, const void* fill_value, unsigned char* d_status, void* stream) {
+    FA_API_LOCK;
+    if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
+    if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
+    if ((out_int == nullptr) == (out_float == nullptr)) return FA_ERROR_CONVERT_TYPE;
+    if (out_float && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
+    if (!fill_value) return FA_ERROR_CONVERT_TYPE;
+    int64_t first_decode, n_decode;
+    int rc = validate_range(stream_size, first_sample, last_sample, &first_decode, &n_decode);
+    if (rc) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ScrubTables tb;
+    if ((rc = scrub_run(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, nch, block_size, d_status, st, &tb))) return rc;
+    const int64_t B = block_size, nf = tb.nf;
+    std::vector<unsigned char> h_status((size_t)(n_stream * nf));
+    FA_HIP_TRY(hipMemcpyAsync(h_status.data(), d_status, h_status.size(), hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    const int64_t f0 = first_decode / B, f1 = (first_decode + n_decode - 1) / B, last_decode = first_decode + n_decode;
+    // runs of frames inside [f0, f1]: decodable ones become slices, the others fill ranges, both clipped to the range
+    std::vector<int64_t> sl_stream, sl_first, sl_count, sl_out, fill_off, fill_count;
+    int64_t n_tasks = 0;
+    for (int64_t s = 0; s < n_stream; ++s) {
+        const unsigned char* row = h_status.data() + s * nf;
+        for (int64_t f = f0; f <= f1;) {
+            const bool good = (row[f] == 0);
+            int64_t g = f + 1;
+            while (g <= f1 && (row[g] == 0) == good) ++g;
+            const int64_t lo = std::max(f * B, first_decode), hi = std::min(g * B, last_decode);
+            if (good) {
+                sl_stream.push_back(s); sl_first.push_back(lo); sl_count.push_back(hi - lo); sl_out.push_back(s * n_decode + (lo - first_decode));
+                n_tasks += g - f;
+            } else {
+                fill_off.push_back(s * n_decode + (lo - first_decode)); fill_count.push_back(hi - lo);
+            }
+            f = g;
+        }
+    }
+    // the decode reads the tolerant tables as an index: it looks at neither d_starts / d_nbytes nor the strict K6
+    DecodeIndex ix;
+    ix.bytes = tb.bytes; ix.n_bytes = n_bytes; ix.n_stream = n_stream; ix.stream_size = stream_size; ix.nf = nf;
+    ix.B = (int32_t)B; ix.nch = nch; ix.meta = tb.meta; ix.ftab = tb.ftab; ix.err = tb.err;
+    (void)hipGetDevice(&ix.device);
+    int32_t* o_i32 = nch == 1 ? static_cast<int32_t*>(out_int) : nullptr;
+    float* o_f32 = nch == 1 ? static_cast<float*>(out_float) : nullptr;
+    int64_t* o_i64 = nch == 2 ? static_cast<int64_t*>(out_int) : nullptr;
+    double* o_f64 = nch == 2 ? static_cast<double*>(out_float) : nullptr;
+    const float* off32 = nch == 1 ? static_cast<const float*>(d_offsets) : nullptr;
+    const float* gain32 = nch == 1 ? static_cast<const float*>(d_gains) : nullptr;
+    const double* off64 = nch == 2 ? static_cast<const double*>(d_offsets) : nullptr;
+    const double* gain64 = nch == 2 ? static_cast<const double*>(d_gains) : nullptr;
+    if (fill_off.empty())  // every frame of the range is intact: the ordinary grid-mode decode (the frames were just checked: verify = 0)
+        return decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, first_decode, n_decode, -1, nullptr, nullptr, nullptr, nullptr, o_i32, o_f32,
+                                  off32, gain32, st, nch, o_i64, o_f64, off64, gain64, &ix, false, 0);
+    {
+        const int64_t nr = (int64_t)fill_off.size();
+        void* pr = nullptr;
+        if ((rc = get_scratch(21, (size_t)nr * 16 + 256, &pr))) return rc;
+        int64_t* d_off = reinterpret_cast<int64_t*>(pr);
+        int64_t* d_cnt = d_off + nr;
+        FA_HIP_TRY(hipMemcpyAsync(d_off, fill_off.data(), (size_t)nr * 8, hipMemcpyHostToDevice, st));
+        FA_HIP_TRY(hipMemcpyAsync(d_cnt, fill_count.data(), (size_t)nr * 8, hipMemcpyHostToDevice, st));
+        void* const out = out_int ? out_int : out_float;
+        if (nch == 1) { if (out_float) launch_fill<float>(out, nr, d_off, d_cnt, fill_value, st); else launch_fill<int32_t>(out, nr, d_off, d_cnt, fill_value, st); }
+        else { if (out_float) launch_fill<double>(out, nr, d_off, d_cnt, fill_value, st); else launch_fill<int64_t>(out, nr, d_off, d_cnt, fill_value, st); }
+        FA_HIP_TRY(hipGetLastError());
+    }
+    if (!sl_stream.empty()) {
+        void* pk = nullptr;
+        const size_t task_bytes = 5 * align_up((size_t)n_tasks * 8, 256);
+        if ((rc = get_scratch(20, task_bytes + 4096, &pk))) return rc;
+        ix.tasks = pk; ix.tasks_bytes = task_bytes + 4096;  // (large enough: the decode never grows, and never owns, this table)
+        rc = decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, (int64_t)sl_stream.size(), sl_stream.data(), sl_first.data(), sl_count.data(),
+                                sl_out.data(), o_i32, o_f32, off32, gain32, st, nch, o_i64, o_f64, off64, gain64, &ix, false, 0);
+    }
+    FA_HIP_TRY(hipStreamSynchronize(st));  // (the fill ranges' host vectors go out of scope)
+    return rc;
+}
+
+int fa_decode_salvage_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                                 int64_t stream_size, int64_t first_sample, int64_t last_sample, int32_t* d_out_i32, float* d_out_f32,
+                                 const float* d_offsets, const float* d_gains, int64_t block_size, const void* fill_value, unsigned char* d_status,
+                                 void* stream) {
+    return salvage_run(1, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first_sample, last_sample, d_out_i32, d_out_f32, d_offsets,
+                       d_gains, block_size, fill_value, d_status, stream);
+}
+
+int fa_decode_salvage_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                                 int64_t stream_size, int64_t first_sample, int64_t last_sample, int64_t* d_out_i64, double* d_out_f64,
+                                 const double* d_offsets, const double* d_gains, int64_t block_size, const void* fill_value, unsigned char* d_status,
+                                 void* stream) {
+    return salvage_run(2, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first_sample, last_sample, d_out_i64, d_out_f64, d_offsets,
+                       d_gains, block_size, fill_value, d_status, stream);
 }
 
 int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t stream_size, const float* d_quanta,

@@ -19,6 +19,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from .scrub import FRAME_CRC16, FRAME_HEADER, FRAME_OK, FRAME_UNLOCATED, common_block_size  # noqa: F401
 
 flac_i32_dtype = np.dtype(np.int32)
 flac_i64_dtype = np.dtype(np.int64)
@@ -1143,6 +1144,108 @@ def decode_flac_device(compressed, starts, nbytes, stream_size, first_sample=-1,
     if errcode != 0:
         return _device_regroup(errcode, out, compressed, starts, nbytes, stream_size, first_sample, last_sample, offsets, gains, False, verify)
     return out
+
+
+def _store_checks(compressed, starts, nbytes, stream_size):
+    """The argument checks of decode_flac_device on a store."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise RuntimeError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64:
+        raise RuntimeError("starts data should be of type int64")
+    if nbytes.dtype != torch.int64:
+        raise RuntimeError("nbytes data should be of type int64")
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise RuntimeError("Only C-contiguous arrays are supported")
+    if stream_size <= 0:
+        raise RuntimeError("You must specify the non-zero output stream size")
+
+
+def _block_size_arg(compressed, starts, nbytes, block_size):
+    """The block size of a damage-map call: the caller's, or the most common STREAMINFO block size among the streams
+    whose first 12 bytes can be read (found on the host, as _blocksize_classes reads them)."""
+    if block_size is not None:
+        if not 1 <= int(block_size) <= 65535:
+            raise RuntimeError("block_size must lie in 1..65535")
+        return int(block_size)
+    torch = _torch()
+    st, nb = starts.reshape(-1), nbytes.reshape(-1)
+    ok = (st >= 0) & (nb >= 12) & (st <= compressed.numel() - 12)
+    st = st[ok]
+    b = None
+    if st.numel():
+        b = common_block_size(compressed[st[:, None] + torch.arange(12, device=st.device)[None, :]].cpu().numpy())
+    if b is None:
+        raise RuntimeError("No stream header gives a block size: pass block_size")
+    return b
+
+
+def frame_status_device(compressed, starts, nbytes, stream_size, is_int64=False, block_size=None):
+    """The damage map of a device-resident store: a uint8 tensor of shape starts.shape + (nf,), nf = ceil(stream_size /
+    block_size), one status per (stream, frame) -- 0 (FRAME_OK), FRAME_UNLOCATED, or FRAME_HEADER | FRAME_CRC16 bits
+    (flacarray_amd/scrub.py; the rule is in DESIGN.md, "Damage map and salvage").  Computed on the GPU from nothing but
+    the store, and never raises for damage: a frame is decodable exactly when its status is 0.  As strong as CRC-16
+    (a random change escapes with probability 2^-16; check_md5_device is the stronger check).  block_size=None: the
+    most common STREAMINFO block size among the streams whose header can be read."""
+    torch = _torch()
+    _store_checks(compressed, starts, nbytes, stream_size)
+    dev = compressed.device
+    with _on_device(dev):
+        B = _block_size_arg(compressed, starts, nbytes, block_size)
+        nf = -(-stream_size // B)
+        n_stream = int(np.prod(starts.shape))
+        status = torch.empty(tuple(starts.shape) + (nf,), dtype=torch.uint8, device=dev)
+        errcode = _lib.lib().fa_frame_status_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size,
+                                                    2 if is_int64 else 1, B, _dp(status), _stream_ptr())
+    if errcode != 0:
+        raise RuntimeError(f"Frame status failed, return code = {errcode}")
+    return status
+
+
+def decode_flac_salvage_device(compressed, starts, nbytes, stream_size, first_sample=-1, last_sample=-1, offsets=None, gains=None,
+                               is_int64=False, fill=None, block_size=None):
+    """Decode through errors: (out, status).  `status` is frame_status_device's map of the whole store; `out` has the
+    dtype and shape of decode_flac_device(...) -- every frame of status 0 decoded exactly, the samples of every other
+    frame set to `fill` (None: 0 for integer output, NaN for float output).  Argument checks and their messages are
+    decode_flac_device's; damage never raises."""
+    torch = _torch()
+    _store_checks(compressed, starts, nbytes, stream_size)
+    n_decode = stream_size
+    if first_sample >= 0 and last_sample >= 0:
+        if last_sample > stream_size:
+            raise RuntimeError("last_sample is beyond end of stream")
+        if first_sample > stream_size - 1:
+            raise RuntimeError("first_sample is beyond last element of stream")
+        if first_sample >= last_sample:
+            raise RuntimeError("first_sample is larger than last_sample")
+        n_decode = last_sample - first_sample
+    if (offsets is None) != (gains is None):
+        raise RuntimeError("When specifying offsets, you must also provide the gains")
+    n_stream = int(np.prod(starts.shape))
+    dev = compressed.device
+    if offsets is None:
+        np_dt, t_dt = (np.int64, torch.int64) if is_int64 else (np.int32, torch.int32)
+    else:
+        np_dt, t_dt = (np.float64, torch.float64) if is_int64 else (np.float32, torch.float32)
+    if fill is None:
+        fill = 0 if offsets is None else np.nan
+    fill_value = np.array([fill], dtype=np_dt)
+    L = _lib.lib()
+    with _on_device(dev):
+        B = _block_size_arg(compressed, starts, nbytes, block_size)
+        nf = -(-stream_size // B)
+        status = torch.empty(tuple(starts.shape) + (nf,), dtype=torch.uint8, device=dev)
+        out = torch.empty(tuple(starts.shape) + (n_decode,), dtype=t_dt, device=dev)
+        if offsets is not None:
+            offsets = offsets.to(device=dev, dtype=t_dt).contiguous()
+            gains = gains.to(device=dev, dtype=t_dt).contiguous()
+        fn = L.fa_decode_salvage_i64_device if is_int64 else L.fa_decode_salvage_i32_device
+        o_int, o_float = (_dp(out), None) if offsets is None else (None, _dp(out))
+        errcode = fn(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first_sample, last_sample,
+                     o_int, o_float, _dp(offsets), _dp(gains), B, _ptr(fill_value), _dp(status), _stream_ptr())
+    if errcode != 0:
+        raise RuntimeError(f"Decoding failed, return code = {errcode}")
+    return out, status
 
 
 def decode_slices_device(compressed, starts, nbytes, stream_size, slice_stream, slice_first, slice_count, offsets=None, gains=None,

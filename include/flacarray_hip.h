@@ -413,6 +413,47 @@ int fa_reduce_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const in
 int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
                       int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
 
+/* ---- damage map and decode through errors.  The decode, compare, reduce and MD5 entry points give up a whole call for one
+ * bad frame; these answer per (stream, frame), from nothing but the store, and decode what is intact.
+ * fa_frame_status_device writes d_status[n_stream][nf] (device, one byte each), nf = ceil(stream_size / block_size):
+ *   FA_FRAME_OK 0; FA_FRAME_UNLOCATED 1: the frame's extent is not known -- its stream is not wholly inside the blob, does
+ *   not begin with "fLaC", its metadata chain does not parse inside nbytes, its STREAMINFO does not say min == max block
+ *   size == block_size with `channels` channels (1: int32 / float32 arrays, 2: int64 / float64), it has no SEEKTABLE of
+ *   exactly nf points, or seek point f or f + 1 does not carry its own sample number or gives an extent that is not at
+ *   least 8 bytes inside the stream (a bad seek point k therefore marks frames k - 1 and k; streams without a per-frame
+ *   SEEKTABLE, such as libFLAC's, are UNLOCATED throughout); for located frames the two independent bits
+ *   FA_FRAME_HEADER 2: the frame header is one the decoder rejects (sync / reserved bits, block-size, sample-rate,
+ *   sample-size or channel code, CRC-8), its number is not f, or its block size is not min(block_size, stream_size - f *
+ *   block_size); FA_FRAME_CRC16 4: the CRC-16 of the frame's bytes is not the stored one.
+ * A frame is decodable exactly when its status is 0.  The check is as strong as CRC-16: a random change escapes it with
+ * probability 2^-16 (fa_check_md5_device is the stronger check, per stream).  However damaged the store is the return
+ * code is FA_ERROR_NONE: non-zero means bad arguments (n_stream <= 0, stream_size <= 0, block_size outside 1..65535,
+ * channels not 1 or 2, a null pointer) or a HIP failure.  No byte is read before its offset is checked against the blob.
+ * fa_fill_ranges_device writes the element at fill_value (host, elem_bytes = 4 or 8 bytes) over n_ranges ranges of d_out:
+ * elements [d_off[i], d_off[i] + d_count[i]) (device arrays; any alignment); nothing else is written; not waited for.
+ * fa_decode_salvage_i32_device / _i64_device take the arguments of fa_decode_i32_device / fa_decode_i64_device (the range,
+ * an integer or a float output, offsets and gains) and block_size, fill_value (host; one output element) and d_status: the
+ * status pass runs over the whole store and lands in d_status, every frame of status 0 that touches the range is decoded
+ * exactly (frame CRC-16 check off: it has just been made), and the samples of every other frame are fill_value.  An error
+ * the decoder still reports (a CRC-clean frame beyond its subset) is returned as by fa_decode_*_device.
+ * All work is issued on `stream`; the status and salvage calls synchronise it before returning. ---- */
+#define FA_FRAME_OK 0
+#define FA_FRAME_UNLOCATED 1
+#define FA_FRAME_HEADER 2
+#define FA_FRAME_CRC16 4
+int fa_frame_status_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                           int64_t stream_size, int channels, int64_t block_size, unsigned char* d_status, void* stream);
+int fa_fill_ranges_device(void* d_out, int elem_bytes, int64_t n_ranges, const int64_t* d_off, const int64_t* d_count, const void* fill_value,
+                          void* stream);
+int fa_decode_salvage_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                                 int64_t stream_size, int64_t first_sample, int64_t last_sample, int32_t* d_out_i32, float* d_out_f32,
+                                 const float* d_offsets, const float* d_gains, int64_t block_size, const void* fill_value, unsigned char* d_status,
+                                 void* stream);
+int fa_decode_salvage_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                                 int64_t stream_size, int64_t first_sample, int64_t last_sample, int64_t* d_out_i64, double* d_out_f64,
+                                 const double* d_offsets, const double* d_gains, int64_t block_size, const void* fill_value, unsigned char* d_status,
+                                 void* stream);
+
 /* Batched random access: slice i is samples [first[i], first[i]+count[i]) of stream
  * slice_stream[i]; its samples are written at element offset out_offset[i] of the output.
  * The four slice arrays are HOST arrays of length n_slices.  The reference needs one
@@ -479,7 +520,7 @@ const char* fa_version(void);
  * do not / process default, see fa_set_decode_verify; revision 3 added the std entry points, revision 4 the compare entry
  * points and fa_set_encode_verify); a binding built against
  * another revision must refuse the library instead of calling it with a shifted argument list --
- * flacarray_amd/_lib.py does.  Entry points that are only added (the append, MD5 and overwrite groups) leave it as it is. */
+ * flacarray_amd/_lib.py does.  Entry points that are only added (the append, MD5, overwrite and damage-map groups) leave it as it is. */
 #define FA_ABI_VERSION 4  /* (revision 4: fa_compare_i32_device / fa_compare_i64_device / fa_set_encode_verify) */
 int fa_abi_version(void);
 
