@@ -28,6 +28,7 @@ from .libflacarray import (
     md5_device,
     overwrite_flac_device,
     reduce_flac_device,
+    reindex_flac_device,
     set_decode_verify,
     set_encode_md5,
     set_encode_verify,
@@ -48,6 +49,7 @@ __all__ = [
     "DeviceDecodeIndex",
     "append_flac_device",
     "overwrite_flac_device",
+    "reindex_flac_device",
     "array_compress",
     "array_decompress",
     "array_decompress_slice",

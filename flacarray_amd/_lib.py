@@ -78,6 +78,8 @@ SYMBOLS = [
     "fa_fill_ranges_device",
     "fa_decode_salvage_i32_device",
     "fa_decode_salvage_i64_device",
+    "fa_reindex_capacity_bytes",
+    "fa_reindex_device",
     "fa_encode_f32_host",
     "fa_encode_f64_host",
     "fa_decode_f32_host",
@@ -244,6 +246,10 @@ def lib():
     for name in ("fa_decode_salvage_i32_device", "fa_decode_salvage_i64_device"):
         getattr(L, name).argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp]
         getattr(L, name).restype = cint
+    L.fa_reindex_capacity_bytes.argtypes = [i64, i64, i64, i64]
+    L.fa_reindex_capacity_bytes.restype = i64
+    L.fa_reindex_device.argtypes = [vp, i64, vp, vp, i64, i64, cint, vp, i64, vp, vp, pi64, vp]
+    L.fa_reindex_device.restype = cint
     L.fa_set_encode_md5.argtypes = [cint]
     L.fa_set_encode_md5.restype = cint
     L.fa_profile_enable.argtypes = [cint]

@@ -515,20 +515,77 @@ class FlacArray:
         limbs = (None, None) if qh is None else (qh.view(np.uint64).reshape(shape), ql.view(np.uint64).reshape(shape))
         return StreamStats(count, lo, hi, sm.reshape(shape), limbs[0], limbs[1], mn.reshape(shape), mx.reshape(shape), off, gain)
 
-    def _splice_layout(self, level, what):
-        """The layout a splice (append, overwrite) needs, checked on the host copy: STREAMINFO with the block size of
-        `level`, then the SEEKTABLE (last) of one point per frame.  Returns (blob, starts, nbytes) as flat numpy arrays."""
+    def _frame_index_layout(self):
+        """The layout test of the host copy: (blob, starts, nbytes, block sizes, own) as flat numpy arrays, `own` True when
+        every stream is "fLaC", STREAMINFO (not last), then the SEEKTABLE (last) of one point per frame; None (and no
+        block sizes) when the stream index does not fit the compressed bytes."""
         st = self._st
-        B = 1152 if level <= 2 else 4096
         blob = np.asarray(st.blob, dtype=np.uint8)
         s0 = np.asarray(st.starts, dtype=np.int64).reshape(-1)
         nb = np.asarray(st.nbytes_per_stream, dtype=np.int64).reshape(-1)
         if np.any(nb < 46) or np.any(s0 < 0) or np.any(s0 + nb > blob.size):
-            raise ValueError("the store's stream index does not fit its compressed bytes")
+            return blob, s0, nb, None, None
         at = lambda k: blob[s0 + k].astype(np.int64)  # noqa: E731
         bs = (at(8) << 8) | at(9)
         stl = (at(43) << 16) | (at(44) << 8) | at(45)
-        if np.any(at(4) != 0) or np.any(at(42) != 0x83) or np.any(stl != 18 * (-(-st.samples // np.maximum(bs, 1)))):
+        own = not (np.any(at(4) != 0) or np.any(at(42) != 0x83) or np.any(stl != 18 * (-(-st.samples // np.maximum(bs, 1)))))
+        return blob, s0, nb, bs, own
+
+    @property
+    def has_frame_index(self):
+        """True when every stream has this library's layout (STREAMINFO, then a SEEKTABLE of one point per frame), which
+        append, overwrite, frame_status and salvage need; False for a store libFLAC wrote (reindex() adopts it).  Host
+        only: read from the stream headers of the host copy, at whatever level the store was written."""
+        return bool(self._frame_index_layout()[4])
+
+    def reindex(self, verify=True):
+        """Adopt a store written by stock flacarray / libFLAC, in place; returns self (addition to the reference API).
+
+        Every stream is copied on the device into this library's layout (reindex_flac_device): its STREAMINFO verbatim (a
+        signed stream stays signed, `md5` does not change), a SEEKTABLE of one point per frame, its frames verbatim.  No
+        sample is decoded or re-encoded, so every value the array decodes to, and `stream_offsets`, `stream_gains`,
+        `shape` and `dtype`, stay what they were; `compressed`, `stream_starts` and `stream_nbytes` change.  After it
+        `has_frame_index` is True: append and overwrite work (at the level whose block size the streams have),
+        frame_status, salvage and damaged_ranges locate the frames, and decodes no longer scan for them.  Every other
+        metadata block of the source (VORBIS_COMMENT, APPLICATION, PADDING, a sparse SEEKTABLE) is dropped.  A store that
+        already has the layout comes out byte-identical.
+
+        `verify=True`: frame_status of the RESULT must be all zero, else RuntimeError and the array stays as it was -- a
+        damaged source frame or a false sync code cannot slip into the index silently.  `verify=False` adopts the store
+        as it is: the way to salvage() a damaged libFLAC-written store (except damage to the header of a stream's last
+        frame, which is refused as a wrong stream size is: that header ties the stream size to the store).  Streams that differ in block size raise
+        ValueError; what the decoders cannot index (variable block sizes, broken headers) raises RuntimeError.
+
+        The store is replaced, not changed: a FlacArray(self) copy made before still holds the old one.  A resident
+        array (to_device / from_device_array) stays resident, with an exact-size blob, and its decode index is rebuilt
+        on next use; any other array uploads its store, reindexes it and brings the result back.  A store assembled by
+        `dist` (global shape other than the local one) raises NotImplementedError."""
+        from .libflacarray import reindex_flac_device
+
+        st = self._st
+        if st.global_shape != st.grid:
+            raise NotImplementedError("reindex is not supported for a store that is one part of a distributed array")
+        res = self._resident
+        _, comp, starts, nbytes = self._device_store()
+        comp2, starts2, nbytes2 = reindex_flac_device(comp, starts, nbytes, st.samples, is_int64=st.wide, verify=verify, compact=res is not None)
+        ishape = np.shape(st.starts)
+        new = _Store.build(st.shape, None, st.dtype, comp2.cpu().numpy(), starts2.cpu().numpy().reshape(ishape),
+                           nbytes2.cpu().numpy().reshape(ishape), st.offsets, st.gains, st.dist)
+        if res is not None:
+            if res.get("index") is not None:
+                res["index"].close()
+            self._resident = dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), index=None)
+        self._st = new
+        return self
+
+    def _splice_layout(self, level, what):
+        """The layout a splice (append, overwrite) needs, checked on the host copy: STREAMINFO with the block size of
+        `level`, then the SEEKTABLE (last) of one point per frame.  Returns (blob, starts, nbytes) as flat numpy arrays."""
+        B = 1152 if level <= 2 else 4096
+        blob, s0, nb, bs, own = self._frame_index_layout()
+        if own is None:
+            raise ValueError("the store's stream index does not fit its compressed bytes")
+        if not own:
             raise ValueError(f"{what} needs streams written by this library (a SEEKTABLE with one point per frame); "
                              "libFLAC-written streams are not supported")
         if np.any(bs != B):
@@ -555,8 +612,8 @@ class FlacArray:
         that PCIe transfer (and, for a host array, the upload) costs more than the device work.  The store is replaced, not
         changed: a FlacArray(self) copy made before still holds the old one.  `verify`: decode the re-encoded span and
         compare it with its input on the device before returning (None = the default of set_encode_verify).  Streams
-        without this library's SEEKTABLE (libFLAC-written) raise ValueError; a store assembled by `dist` (global shape
-        other than the local one) raises NotImplementedError.
+        without this library's SEEKTABLE (libFLAC-written) raise ValueError -- reindex() adopts such a store first; a
+        store assembled by `dist` (global shape other than the local one) raises NotImplementedError.
 
         The splice writes a fresh stream header, so the appended store comes out UNSIGNED (`md5` all zero) even if the
         old one was signed: a finished digest cannot be resumed.  `md5=True` is append followed by sign(): correct, at the
@@ -607,8 +664,8 @@ class FlacArray:
         array uploads its store, patches it on the device and brings the result back.  The store is replaced, not
         changed: a FlacArray(self) copy made before still holds the old one.  `verify`: decode the re-encoded span and
         compare it with its input on the device before returning (None = the default of set_encode_verify).  Streams
-        without this library's SEEKTABLE (libFLAC-written) raise ValueError; a store assembled by `dist` raises
-        NotImplementedError.
+        without this library's SEEKTABLE (libFLAC-written) raise ValueError -- reindex() adopts such a store first; a
+        store assembled by `dist` raises NotImplementedError.
 
         A stream that takes part comes out UNSIGNED (its STREAMINFO MD5 zeroed: its samples changed); a stream that does
         not keeps its header, and so a valid signature, verbatim.  `md5=True` is overwrite followed by sign()."""
@@ -698,7 +755,8 @@ class FlacArray:
         """The damage map of the store as it is held: numpy uint8 of shape leading_shape + (nf,), one status per
         (stream, frame) -- 0 = decodable, FRAME_UNLOCATED, or FRAME_HEADER | FRAME_CRC16 bits (flacarray_amd.scrub).
         Computed on the device from the resident store (or an upload), never through the decode index, and never
-        raises for damage.  As strong as CRC-16: check_md5() is the stronger check, per stream."""
+        raises for damage.  As strong as CRC-16: check_md5() is the stronger check, per stream.  A libFLAC-written store
+        has no seek point per frame, so all its frames are FRAME_UNLOCATED: reindex() adopts it first."""
         from .libflacarray import frame_status_device
 
         _, comp, st, nb, _, _ = self._device_store(scale=True)
@@ -708,7 +766,8 @@ class FlacArray:
     def salvage(self, stream_slice=None, fill=None):
         """Decode through errors: (array, status).  `array` is shaped as to_array(stream_slice=...) shapes it (same
         step-1 slice rules): every frame whose status is 0 decoded exactly, the samples of every other frame set to
-        `fill` (None: 0 for an integer store, NaN for a float store); `status` is frame_status() of the whole store."""
+        `fill` (None: 0 for an integer store, NaN for a float store); `status` is frame_status() of the whole store.
+        A libFLAC-written store is all FRAME_UNLOCATED, hence all fill: reindex(verify=False) adopts it first."""
         from .libflacarray import decode_flac_salvage_device
 
         lo, hi = -1, -1

@@ -41,6 +41,7 @@
 #include "md5_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "scrub_kernels.hpp"
+#include "reindex_kernels.hpp"
 
 namespace {
 
@@ -59,7 +60,7 @@ using namespace fa;
 // device share its cached scratch buffers); calls that target different devices -- one process driving several
 // GPUs from several threads -- do not serialise each other.  g_mu guards the map of device states only.
 constexpr int kProfPairs = 6;
-constexpr int kScratchSlots = 22;
+constexpr int kScratchSlots = 23;
 struct DeviceState {
     std::recursive_mutex api_mu;
     std::map<int, float*> windows;  // blocksize -> device tukey(0.5) table
@@ -69,7 +70,8 @@ struct DeviceState {
     // [14]: the MD5 check's decoded column chunk, [15]: its chaining states, digests and flags (fa_check_md5_device);
     // [16]: the binned reduction's decoded column chunk (fa_reduce_*);
     // [17]: the damage map's realigned blob, [18]: its tolerant stream table, flags and error block, [19]: its tolerant frame
-    // table, [20]: the salvage decode's task table, [21]: its fill ranges (fa_frame_status_device, fa_decode_salvage_*)
+    // table, [20]: the salvage decode's task table, [21]: its fill ranges (fa_frame_status_device, fa_decode_salvage_*);
+    // [22]: the reindex's error word and total (fa_reindex_device; its realigned source blob is the decoders', [7])
     void* scratch[kScratchSlots] = {};
     size_t scratch_bytes[kScratchSlots] = {};
     uint64_t scratch_epoch = 1;  // bumped whenever a scratch slot is (re)allocated or released: cached contents are then stale
@@ -2514,6 +2516,88 @@ int fa_decode_salvage_i64_device(const unsigned char* d_bytes, int64_t n_bytes, 
                                  void* stream) {
     return salvage_run(2, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first_sample, last_sample, d_out_i64, d_out_f64, d_offsets,
                        d_gains, block_size, fill_value, d_status, stream);
+}
+
+// ---- reindex (reindex_kernels.hpp) ----
+int64_t fa_reindex_capacity_bytes(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t block_size) {
+    if (n_old_bytes < 0 || n_stream < 0 || stream_size <= 0 || block_size < 1 || block_size > 65535) return -1;
+    const int64_t nf = (stream_size + block_size - 1) / block_size;
+    if (nf > kReindexMaxFrames) return -1;
+    if (n_stream > 0 && stream_header_bytes(nf) > (INT64_MAX - n_old_bytes) / n_stream) return -1;
+    return n_old_bytes + n_stream * stream_header_bytes(nf);  // (an upper bound: the bodies are part of the old bytes)
+}
+
+// K6's tables of the caller's store (built as a decode index is, freed on return), the check, the sizes and starts (one
+// wait: the error word and the total), then the copy.  Nothing is written to d_bytes unless every check passed.
+// Every launch and copy is on the caller's stream; the tables, like a decode index's, come from hipMalloc and go back
+// with hipFree, and both wait for the whole device -- a one-time migration pays that, a call per read would not.
+int fa_reindex_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                      int64_t n_stream, int64_t stream_size, int n_channels, unsigned char* d_bytes, int64_t capacity_bytes,
+                      int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream) {
+    FA_API_LOCK;
+    if (!h_total_bytes) return FA_ERROR_ALLOC;
+    *h_total_bytes = 0;
+    if (n_stream < 0) return FA_ERROR_ZERO_NSTREAM;
+    if (n_stream == 0) return FA_ERROR_NONE;  // an empty store: nothing to launch
+    if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
+    if (n_channels != 1 && n_channels != 2) return FA_ERROR_CONVERT_TYPE;
+    if (n_old_bytes <= 0 || !d_old || !d_old_starts || !d_old_nbytes || !d_starts || !d_nbytes) return FA_ERROR_DECODE_INIT;
+    if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // K6's 16-byte loads are issued relative to the blob base: realign as the decoders do, into their slot (calls are
+    // serialised by api_mu and each writes the slot before it reads it, so one store-sized buffer serves both)
+    if (reinterpret_cast<uintptr_t>(d_old) & 15) {
+        void* al = nullptr;
+        int rc0 = get_scratch(7, (size_t)n_old_bytes + 256, &al);
+        if (rc0) return rc0;
+        FA_HIP_TRY(hipMemcpyAsync(al, d_old, (size_t)n_old_bytes, hipMemcpyDeviceToDevice, st));
+        d_old = reinterpret_cast<const unsigned char*>(al);
+    }
+    DecodeIndex ix;
+    struct Tables {  // (hipFree waits for the device: the kernels that read the tables are done)
+        DecodeIndex* ix;
+        ~Tables() {
+            if (ix->meta) (void)hipFree(ix->meta);
+            if (ix->ftab) (void)hipFree(ix->ftab);
+        }
+    } tables{&ix};
+    int rc = decode_device_impl(d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, 0, 0, -1, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, nullptr, nullptr, nullptr, st, n_channels, nullptr, nullptr, nullptr, nullptr, &ix, true);
+    if (rc) return rc;  // (K6's own errors: a bad header, variable or mixed block sizes, a walk that runs off its stream)
+    if (ix.nf > kReindexMaxFrames) return FA_ERROR_DECODE_INIT;
+    const int64_t nt = n_stream * ix.nf;
+    if (nt >= (1LL << 31) * 256) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    void* ps = nullptr;
+    if ((rc = get_scratch(22, 256, &ps))) return rc;
+    ReindexArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.src = d_old; a.src_bytes = n_old_bytes; a.src_starts = d_old_starts; a.meta = ix.meta; a.ftab = ix.ftab;
+    a.starts = d_starts; a.nbytes = d_nbytes; a.out = d_bytes;
+    a.err = reinterpret_cast<int*>(ps);
+    a.n_stream = n_stream; a.nf = ix.nf; a.stream_size = stream_size; a.B = ix.B;
+    int64_t* d_total = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ps) + 8);
+    FA_HIP_TRY(hipMemsetAsync(ps, 0, 16, st));
+    hipLaunchKernelGGL(reindex_check_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(reindex_size_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_nbytes, n_stream, d_starts, d_total);
+    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
+    FA_HIP_TRY(hipMemcpyAsync(&back, ps, sizeof back, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (back.err & kReindexBadHeader) return FA_ERROR_DECODE_INIT;
+    if (back.err & kReindexBadTable) return FA_ERROR_DECODE_SEEK;
+    if (back.err) return FA_ERROR_DECODE_STREAMSIZE;  // (the last frame is not frame nf - 1 of the stream_size given)
+    if (back.total > capacity_bytes) return FA_ERROR_ALLOC;
+    // workgroups per stream: ~64 KB of the result each (at most 1024, and a grid of fewer than 2^23 workgroups)
+    int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, back.total / n_stream / 65536));
+    while (parts > 1 && n_stream * parts >= (1LL << 23)) parts >>= 1;
+    if (n_stream * parts >= (1LL << 23)) return FA_ERROR_DECODE_SAMPLE_RANGE;  // (parts == 1: more streams than a grid takes)
+    a.parts = (int32_t)parts;
+    hipLaunchKernelGGL(reindex_kernel, dim3((unsigned)(n_stream * parts)), dim3(256), 0, st, a);
+    FA_HIP_TRY(hipGetLastError());
+    FA_HIP_TRY(hipStreamSynchronize(st));  // (the tables are freed on return, the scratch is the next call's)
+    *h_total_bytes = back.total;
+    return FA_ERROR_NONE;
 }
 
 int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t stream_size, const float* d_quanta,

@@ -1769,3 +1769,71 @@ def overwrite_flac_device(compressed, starts, nbytes, stream_size, first, data, 
     if n == 0 or (idx is not None and idx.size == 0):
         return compressed, starts, nbytes
     return _splice_flac_device("overwrite", compressed, starts, nbytes, stream_size, data, idx, first, level, offsets, gains, verify, compact)
+
+
+def reindex_flac_device(compressed, starts, nbytes, stream_size, is_int64=False, verify=True, compact=False):
+    """Adopt a device-resident store written by another FLAC encoder (stock flacarray / libFLAC): returns the new
+    (compressed, starts, nbytes), all on the device, the store's arguments left as they are.
+
+    Every stream is copied into this library's own layout -- "fLaC", the source's STREAMINFO verbatim (a signed stream
+    stays signed), a SEEKTABLE of one point per frame, the frames verbatim (fa_reindex_device, include/flacarray_hip.h).
+    No sample is decoded and nothing is re-encoded; after it append_flac_device, overwrite_flac_device,
+    frame_status_device and decode_flac_salvage_device take the store, and a decode no longer scans for the frames.
+    Every other metadata block of the source (VORBIS_COMMENT, APPLICATION, PADDING, a sparse or placeholder SEEKTABLE) is
+    dropped: the layout has no room for it.  A store that already has the layout comes out byte-identical.  is_int64:
+    two-channel streams (int64 / float64 arrays).  The streams of one call share their block size, as the streams stock
+    flacarray writes at one level do: a store that mixes block sizes raises ValueError (reindex its parts).  Anything the
+    decoders would refuse when they index the store (a header that does not parse, a variable block size, the other
+    channel count, a wrong stream_size, a SEEKTABLE whose offsets leave the stream) raises RuntimeError.
+
+    `compressed` is a view of a buffer sized for the worst case (the old bytes plus the new headers), which it keeps
+    alive; `compact=True` returns an exact-size copy instead, as the splice functions do.  `verify=True` (the default)
+    runs frame_status_device over the RESULT and raises RuntimeError unless every status is 0: every located frame then
+    carries its number, its block size and a clean CRC-16, so a false sync code or a damaged source frame cannot slip
+    into an index silently -- cheap next to a one-time migration.  `verify=False` skips it: the way to adopt a damaged
+    store in order to salvage it -- with one exception: the header of every stream's LAST frame must still carry its frame
+    number and block size, because that is what ties `stream_size` to the store (RuntimeError otherwise, as for a wrong
+    stream_size)."""
+    torch = _torch()
+    _store_checks(compressed, starts, nbytes, stream_size)
+    if starts.shape != nbytes.shape:
+        raise RuntimeError("starts and nbytes should have one shape")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("reindex_flac_device needs compressed, starts and nbytes on the same GPU")
+    n_stream = int(np.prod(starts.shape))
+    if n_stream == 0:
+        return compressed.new_empty(0), starts.clone(), nbytes.clone()
+    L = _lib.lib()
+    with _on_device(dev):
+        st, nb = starts.reshape(-1), nbytes.reshape(-1)
+        B = None
+        if bool(((st >= 0) & (nb >= 12) & (st <= compressed.numel() - 12)).all()):
+            head = compressed[st[:, None] + torch.arange(12, device=dev)[None, :]].cpu().numpy()
+            if _blocksize_classes(head) is not None:
+                raise ValueError("the store's streams differ in block size: reindex takes one block size per call "
+                                 "(reindex the streams of each block size on their own)")
+            B = common_block_size(head)
+        cap = L.fa_reindex_capacity_bytes(compressed.numel(), n_stream, stream_size, B) if B else -1
+        if cap < 0:
+            raise RuntimeError("Reindexing failed: no stream header gives a block size the stream size fits")
+        buf = torch.empty(cap, dtype=torch.uint8, device=dev)
+        index = torch.empty(2 * n_stream, dtype=torch.int64, device=dev)
+        total = ctypes.c_int64(0)
+        errcode = L.fa_reindex_device(_dp(compressed), compressed.numel(), _dp(st), _dp(nb), n_stream, stream_size, 2 if is_int64 else 1,
+                                      _dp(buf), cap, _dp(index[:n_stream]), _dp(index[n_stream:]), ctypes.byref(total), _stream_ptr())
+    if errcode != 0:
+        raise RuntimeError(f"Reindexing failed, return code = {errcode}")
+    blob = buf[: total.value]
+    if compact:
+        blob = blob.clone()
+        del buf
+    out = (blob, index[:n_stream].reshape(starts.shape), index[n_stream:].reshape(starts.shape))
+    if verify:
+        status = frame_status_device(out[0], out[1], out[2], stream_size, is_int64=is_int64, block_size=B)
+        bad = torch.nonzero(status.reshape(n_stream, -1))
+        if bad.numel():
+            s_bad, f_bad = (int(v) for v in bad[0])
+            raise RuntimeError(f"Reindexing failed: {bad.shape[0]} frame(s) of the result do not check (first: stream {s_bad}, frame {f_bad}, "
+                               f"status {int(status.reshape(n_stream, -1)[s_bad, f_bad])}); verify=False adopts the store as it is, for salvage")
+    return out

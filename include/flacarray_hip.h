@@ -454,6 +454,36 @@ int fa_decode_salvage_i64_device(const unsigned char* d_bytes, int64_t n_bytes, 
                                  const double* d_offsets, const double* d_gains, int64_t block_size, const void* fill_value, unsigned char* d_status,
                                  void* stream);
 
+/* Reindex: copy every stream of a store into this library's own layout -- "fLaC", STREAMINFO (the source's 34 bytes
+ * verbatim, MD5 included, marked not last), a SEEKTABLE of one point per frame (sample number f B, offset of frame f from
+ * the first frame, min(B, N - f B) samples), then the source's frames [first frame, end of stream) verbatim.  No sample is
+ * decoded and nothing is re-encoded; every other metadata block of the source (VORBIS_COMMENT, APPLICATION, PADDING, a
+ * sparse or placeholder SEEKTABLE) is dropped; a stream that already has the layout comes out byte-identical.  This is how
+ * a libFLAC-written store, which the decoders read but append, overwrite and the damage map refuse, becomes a store of
+ * this library.  The frames are located as the decoders locate them (a complete SEEKTABLE, else the sync scan, else the
+ * walk), so one call takes streams of ONE block size and n_channels (1: int32 / float32 arrays, 2: int64 / float64), and
+ * the decoders' errors come back as they are: FA_ERROR_DECODE_INIT for a stream header that does not parse, a variable
+ * block size, streams that differ in block size, or the other channel count; FA_ERROR_DECODE_PROCESS for a walk that
+ * leaves its stream.  On top of that the frame table must start at the first frame, increase strictly and leave 8 bytes
+ * for the last frame inside its stream (FA_ERROR_DECODE_SEEK otherwise: the offsets of a SEEKTABLE are the file's word,
+ * and the copy would follow them), the last frame located must carry frame number nf - 1 and the block size that
+ * stream_size leaves for it (FA_ERROR_DECODE_STREAMSIZE: the stream_size is not the store's), the first metadata block
+ * must be a STREAMINFO of 34 bytes, and a stream has at most 932 067 frames, what the SEEKTABLE's 24-bit length holds
+ * (FA_ERROR_DECODE_INIT).  d_old may have any alignment (a
+ * misaligned blob is realigned through the library's scratch) and is unchanged; d_bytes must not overlap it and has room
+ * for capacity_bytes; fa_reindex_capacity_bytes() = n_old_bytes + n_stream * (46 + 18 nf) always suffices (-1 for
+ * arguments that make no store), a smaller buffer gives FA_ERROR_ALLOC if the result does not fit.  On every error
+ * nothing is written to d_bytes.  The new streams lie back to back from 0 in the old order, d_starts / d_nbytes
+ * [n_stream] are their index, *h_total_bytes the bytes used.  n_stream == 0 returns FA_ERROR_NONE with a total of 0 and
+ * launches nothing.  All device work is issued on `stream`, which the call waits for before it returns; the frame tables
+ * are allocated and freed per call as fa_decode_index_create / _destroy do, and those two runtime calls wait for the whole
+ * device, not for `stream` alone.  Because the last frame's header ties stream_size to the store, a store whose damage
+ * sits in the header of a stream's LAST frame is refused (FA_ERROR_DECODE_STREAMSIZE) like a wrong stream_size. */
+int64_t fa_reindex_capacity_bytes(int64_t n_old_bytes, int64_t n_stream, int64_t stream_size, int64_t block_size);
+int fa_reindex_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes,
+                      int64_t n_stream, int64_t stream_size, int n_channels, unsigned char* d_bytes, int64_t capacity_bytes,
+                      int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream);
+
 /* Batched random access: slice i is samples [first[i], first[i]+count[i]) of stream
  * slice_stream[i]; its samples are written at element offset out_offset[i] of the output.
  * The four slice arrays are HOST arrays of length n_slices.  The reference needs one
@@ -520,7 +550,7 @@ const char* fa_version(void);
  * do not / process default, see fa_set_decode_verify; revision 3 added the std entry points, revision 4 the compare entry
  * points and fa_set_encode_verify); a binding built against
  * another revision must refuse the library instead of calling it with a shifted argument list --
- * flacarray_amd/_lib.py does.  Entry points that are only added (the append, MD5, overwrite and damage-map groups) leave it as it is. */
+ * flacarray_amd/_lib.py does.  Entry points that are only added (the append, MD5, overwrite, damage-map and reindex groups) leave it as it is. */
 #define FA_ABI_VERSION 4  /* (revision 4: fa_compare_i32_device / fa_compare_i64_device / fa_set_encode_verify) */
 int fa_abi_version(void);
 
