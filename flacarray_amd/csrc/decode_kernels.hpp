@@ -554,7 +554,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 #define FA_TILE_W 32
 #endif
 #ifndef FA_K7_SPEC
-#define FA_K7_SPEC 0  // experiment (r04, profiles/r04_k7_notes.md): the window's ring words stay in registers and the one word a
+#define FA_K7_SPEC 0  // experiment (r04, profiles/r04_k7_notes.md; measured again on global chunk loads: still 8 % slower, profiles/k7_prefetch.md): the window's ring words stay in registers and the one word a
                       // sample can newly need is requested a sample ahead -- the LDS round trip leaves the loop-carried chain,
                       // two LDS reads per sample go, five vector instructions come: 13 % SLOWER (4.07 against 3.59 ms)
 #endif
@@ -563,6 +563,9 @@ __device__ __forceinline__ void static_for(F&& f) {
 #endif
 #ifndef FA_K7_NT
 #define FA_K7_NT 1  // whole-tile stores bypass the caches (streaming output): -1.5 % in the same-box A/B (r03i)
+#endif
+#ifndef FA_K7_LATE_FLUSH
+#define FA_K7_LATE_FLUSH 1  // a tile is stored at the start of the next macro step, behind the top-up (profiles/k7_prefetch.md)
 #endif
 #ifndef FA_K7_X
 #define FA_K7_X 0  // timing experiments only (results are wrong): 1 = no prediction, 2 = no global stores, 4 = no tile write,
@@ -604,10 +607,11 @@ __device__ __forceinline__ void ring_load_chunk(const uint8_t* cbase, const uint
 struct Chunk {
     uint4 d[kChunkBytes / 16];
 };
-// (The four loads are conditional loads into zero-initialised registers, which makes the compiler wait for the
-// previous load before each of them.  That serialisation is worth keeping: the four pieces share a cache line, the
-// first load brings it into L1 and the other three hit; issued back to back -- unconditional loads from a clamped
-// address -- all four miss and K7 is 12 % slower, profiles/r03_k7_experiments.md.)
+// (The four loads are conditional loads into zero-initialised registers: the compiler zeroes all four destinations
+// behind ONE wait for whatever load still targets them and then issues the loads back to back -- global loads, which
+// count in vmcnt only, so nothing waits for them before the next top-up.  The reading of round 3, that the compiler
+// serialises the four and that this serialisation is what lets pieces 2-4 hit in L1, was taken while these were flat
+// loads and does not describe this code; a staggered issue was not measured again, profiles/k7_prefetch.md.)
 __device__ __forceinline__ Chunk chunk_fetch(const uint8_t* cbase, const uint8_t* lim16, uint32_t ci) {
     const uint8_t* q = cbase + (size_t)ci * kChunkBytes;
     Chunk c;
@@ -843,10 +847,16 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         const int64_t at = a.ftab[s * a.nf + f];
         if (m.first_frame < 0 || at < 0) bad = true;
         else {
-            const uint8_t* start = a.blob + at;
-            cbase = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(start - 1) & ~(uintptr_t)(kChunkBytes - 1));  // bitpos >= 8
-            if (cbase < a.blob) cbase = a.blob;  // the blob base is 16-byte aligned (host side guarantees it)
-            bitpos = (uint32_t)(start - cbase) * 8;
+            // The chunk base is the absolute 64-byte boundary at or below the byte in front of the frame (bitpos >= 8), found
+            // by arithmetic on the OFFSET into the blob: `mis` is how far the blob base lies behind such a boundary.  (A base
+            // rebuilt from the integer address lands on the same byte, but the compiler no longer knows that it points to
+            // global memory: every chunk load became a flat load, which also counts in lgkmcnt, so the sample loop's LDS
+            // waits waited for the prefetch -- profiles/k7_prefetch.md.)
+            const int64_t mis = (int64_t)(reinterpret_cast<uintptr_t>(a.blob) & (uintptr_t)(kChunkBytes - 1));
+            int64_t coff = ((at - 1 + mis) & ~(int64_t)(kChunkBytes - 1)) - mis;
+            if (coff < 0) coff = 0;  // the blob base is 16-byte aligned (host side guarantees it)
+            cbase = a.blob + coff;
+            bitpos = (uint32_t)(at - coff) * 8;
             ring_load_chunk(cbase, lim16, ring, 0);
             ring_load_chunk(cbase, lim16, ring, 1);
             next_chunk = 2;
@@ -1561,8 +1571,18 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                 // least 64 are resident after this top-up -> the sample code needs no residency test
                 topup();
             }
+#if FA_K7_LATE_FLUSH
+            // The previous tile leaves HERE: behind the top-up's wait for its prefetch (loads and stores share vmcnt, so a
+            // store issued in front of that wait is waited for as well) and behind the new prefetch, with eight samples
+            // to go before the next such wait -- and before sample 0 writes the tile image again.
+            if constexpr (u == 0) {
+                if (i0 > 0) flush_tile(i0 - MACRO);
+            }
+#endif
             sample(guard_tag, part_tag, ut, i);
+#if !FA_K7_LATE_FLUSH
             if constexpr (u == MACRO - 1) flush_tile(i0);
+#endif
         });
     };
     // guarded head (warm-up zone), unguarded main part, guarded tail (frames shorter than B).
@@ -1600,6 +1620,9 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             }
         }
     }
+#if FA_K7_LATE_FLUSH
+    if (end > 0) flush_tile(end - MACRO);  // the last tile (the steps above cover [0, end) without a gap)
+#endif
     if constexpr (NCH == 2) {
         if (skipped) {  // on to the second subframe: the reader state at its first bit
             bitpos = resume_bitpos;

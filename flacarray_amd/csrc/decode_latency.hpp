@@ -224,7 +224,8 @@ __global__ __launch_bounds__(64) void decode_latency_kernel(DecodeArgs a, LatInl
     auto give_up = [&](int why) __attribute__((always_inline)) {
         // (a plain store: the word may live in pinned host memory, and all the host asks is "non-zero?"; with several
         // frames giving up the diagnostic shows one of their reasons)
-        if (lane == 0) *reinterpret_cast<volatile int*>(fallback) = why;
+        // (the pointer is given its address space: a volatile access keeps the generic one otherwise, a flat store)
+        if (lane == 0) *(volatile __attribute__((address_space(1))) int*)fallback = why;
     };
 
 #if FA_LAT_STAMPS

@@ -185,11 +185,17 @@ __global__ __launch_bounds__(256) void splice_size_kernel(SpliceArgs a) {
 // Copy [src, src + len) to [dst, dst + len): the 16-byte destination chunks that meet the range are shared out over
 // `nthr` threads (this one is `t`); a chunk inside the range is one uint4 store built from two aligned uint4 loads,
 // a chunk at an edge stores its bytes one by one.  src_end: end of the readable source buffer.
-__device__ __forceinline__ uint4 funnel16(const uint8_t* s, uint32_t q) {
-    const uint8_t* blk = s - q;
-    const uint4 lo = *reinterpret_cast<const uint4*>(blk);
-    if (q == 0) return lo;
-    const uint4 hi = *reinterpret_cast<const uint4*>(blk + 16);
+// Every buffer a segment is copied between is device global memory, and the copy says so: its pointers carry the global
+// address space, and a chunk is addressed by its OFFSET from dst / src.  (Addresses rebuilt from integers, as this code
+// had them, or plain pointer parameters of an out-of-line function are generic: each access was a flat one.)
+typedef __attribute__((address_space(1))) uint8_t g_u8;
+typedef uint32_t g_u32x4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) g_u32x4_t g_u32x4;
+__device__ __forceinline__ uint4 funnel16(const g_u8* s, uint32_t q) {
+    const g_u8* blk = s - q;
+    const g_u32x4_t lo = *reinterpret_cast<const g_u32x4*>(blk);
+    if (q == 0) return make_uint4(lo.x, lo.y, lo.z, lo.w);
+    const g_u32x4_t hi = *reinterpret_cast<const g_u32x4*>(blk + 16);
     const uint32_t sh = q & 3u;
     uint32_t w0, w1, w2, w3, w4;
     switch (q >> 2) {  // (one value for the whole segment: a uniform branch)
@@ -205,10 +211,13 @@ __device__ __forceinline__ uint4 funnel16(const uint8_t* s, uint32_t q) {
 __device__ void copy_segment(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int64_t len, const uint8_t* src_end, int64_t t,
                              int64_t nthr) {
     if (len <= 0) return;
+    g_u8* const gd = (g_u8*)dst;
+    const g_u8* const gs = (const g_u8*)src;
+    const g_u8* const gend = (const g_u8*)src_end;
     const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + (uintptr_t)len;
     const uintptr_t c0 = d0 & ~(uintptr_t)15, c1 = (d1 + 15) & ~(uintptr_t)15;
     const int64_t nchunk = (int64_t)((c1 - c0) >> 4);
-    const int64_t delta = reinterpret_cast<intptr_t>(src) - reinterpret_cast<intptr_t>(dst);
+    const int64_t e0 = -(int64_t)(d0 & 15);  // the first chunk starts this far from dst (0 .. -15)
     const uint32_t q = (uint32_t)(((uintptr_t)src - (uintptr_t)dst) & 15u);
     constexpr int U = 4;  // chunks in flight per thread
     for (int64_t i0 = t; i0 < nchunk; i0 += U * nthr) {
@@ -217,22 +226,24 @@ __device__ void copy_segment(uint8_t* __restrict__ dst, const uint8_t* __restric
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + (int64_t)u * nthr;
-            const uintptr_t c = c0 + ((uintptr_t)i << 4);
-            const uint8_t* s = reinterpret_cast<const uint8_t*>((intptr_t)c + delta);
-            full[u] = i < nchunk && c >= d0 && c + 16 <= d1 && (s - q) + (q ? 32 : 16) <= src_end;
+            const int64_t o = e0 + (i << 4);  // the chunk's offset from dst, and of its source bytes from src
+            const g_u8* s = gs + o;
+            full[u] = i < nchunk && o >= 0 && o + 16 <= len && (s - q) + (q ? 32 : 16) <= gend;
             if (full[u]) v[u] = funnel16(s, q);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + (int64_t)u * nthr;
             if (i >= nchunk) break;
-            const uintptr_t c = c0 + ((uintptr_t)i << 4);
+            const int64_t o = e0 + (i << 4);
             if (full[u]) {
-                *reinterpret_cast<uint4*>(c) = v[u];
+                g_u32x4_t w;
+                w.x = v[u].x; w.y = v[u].y; w.z = v[u].z; w.w = v[u].w;
+                *reinterpret_cast<g_u32x4*>(gd + o) = w;
             } else {  // an edge of the segment (or a source chunk at the end of its buffer)
                 for (int b = 0; b < 16; ++b) {
-                    const uintptr_t d = c + (uintptr_t)b;
-                    if (d >= d0 && d < d1) *reinterpret_cast<uint8_t*>(d) = *reinterpret_cast<const uint8_t*>((intptr_t)d + delta);
+                    const int64_t d = o + b;
+                    if (d >= 0 && d < len) gd[d] = gs[d];
                 }
             }
         }
