@@ -567,6 +567,12 @@ __device__ __forceinline__ void static_for(F&& f) {
 #ifndef FA_K7_LATE_FLUSH
 #define FA_K7_LATE_FLUSH 1  // a tile is stored at the start of the next macro step, behind the top-up (profiles/k7_prefetch.md)
 #endif
+#ifndef FA_K7_STEP_WAIT
+#define FA_K7_STEP_WAIT 1  // the main loop's macro step opens with an explicit `s_waitcnt vmcnt(0)` (profiles/k7_refill.md 1)
+#endif
+#ifndef FA_K7_VOTE
+#define FA_K7_VOTE 1  // one wave vote per refill round replaces the prefetch's four per-piece bounds (profiles/k7_refill.md)
+#endif
 #ifndef FA_K7_X
 #define FA_K7_X 0  // timing experiments only (results are wrong): 1 = no prediction, 2 = no global stores, 4 = no tile write,
                    // 8 = no chunk loads in the sample loop
@@ -1157,6 +1163,18 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             else ring_load_chunk(cbase, lim16, ring, next_chunk);  // a slow read overtook the prefetch
             next_chunk++;
             pend_ci = next_chunk;
+#if FA_K7_VOTE && !(FA_K7_X & 8)
+            // One vote of the lanes that refill: the prefetched chunk ends at or in front of lim16.  q and lim16 are multiples
+            // of 16, so q + 64 <= lim16 is the conjunction of chunk_fetch's four tests q + 16 v + 16 <= lim16: the four loads
+            // then go out as they are -- no zeroed destinations, no compare and no exec region per piece -- and read the
+            // bytes the guarded form reads.  Where some lane's chunk crosses lim16 (the last frames of the blob) the round
+            // runs the guarded form.
+            const uint8_t* q = cbase + (size_t)pend_ci * kChunkBytes;
+            if (__builtin_expect(__ballot(q + kChunkBytes > lim16) == 0ull, 1)) {
+#pragma unroll
+                for (int v = 0; v < kChunkBytes / 16; ++v) pend.d[v] = *reinterpret_cast<const uint4*>(q + 16 * v);
+            } else
+#endif
             pend = chunk_fetch(cbase, lim16, pend_ci);
         }
     };
@@ -1566,6 +1584,18 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         static_for<MACRO>([&](auto ut) __attribute__((always_inline)) {
             constexpr int u = decltype(ut)::value;
             const int i = i0 + u;
+#if FA_K7_STEP_WAIT
+            // The unguarded step without a partition boundary -- the loop the headline workload lives in -- opens with a
+            // full vmcnt wait of its own.  In hardware it waits for nothing new: the loop's latch drains vmcnt before every
+            // step (it moves the prefetched chunk between the two register sets that the allocator keeps for the two
+            // bodies), and the top-up below waits for the same loads.  What it buys is the compiler's bookkeeping: without
+            // it the body is entered with "a load into the other body's set may be in flight", and the first write of such
+            // a register BEHIND the top-up drains vmcnt -- one sample after the tile stores and the new prefetch went out.
+            // It has to stand in this body's own first block: in front of the branch that selects the body, or in both
+            // bodies (the compiler then hoists it there), it changes nothing (profiles/k7_refill.md 1).
+            if constexpr (u == 0 && !decltype(guard_tag)::value && !decltype(part_tag)::value)
+                __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0); expcnt and lgkmcnt left alone
+#endif
             if constexpr ((u % kTopup) == 0) {
                 // all lanes together: the next 8 fast-path samples need at most 32 bytes, and at
                 // least 64 are resident after this top-up -> the sample code needs no residency test
