@@ -34,6 +34,7 @@ from .libflacarray import (
     set_encode_verify,
     sign_streams_device,
     std_device,
+    window_flac_device,
 )
 from .scrub import FRAME_CRC16, FRAME_HEADER, FRAME_OK, FRAME_UNLOCATED, damaged_ranges
 from .utils import float_to_int, int_to_float, keep_select, stream_md5
@@ -50,6 +51,7 @@ __all__ = [
     "append_flac_device",
     "overwrite_flac_device",
     "reindex_flac_device",
+    "window_flac_device",
     "array_compress",
     "array_decompress",
     "array_decompress_slice",

@@ -80,6 +80,9 @@ SYMBOLS = [
     "fa_decode_salvage_i64_device",
     "fa_reindex_capacity_bytes",
     "fa_reindex_device",
+    "fa_window_workspace_bytes",
+    "fa_window_capacity_bytes",
+    "fa_window_device",
     "fa_encode_f32_host",
     "fa_encode_f64_host",
     "fa_decode_f32_host",
@@ -250,6 +253,12 @@ def lib():
     L.fa_reindex_capacity_bytes.restype = i64
     L.fa_reindex_device.argtypes = [vp, i64, vp, vp, i64, i64, cint, vp, i64, vp, vp, pi64, vp]
     L.fa_reindex_device.restype = cint
+    L.fa_window_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, cint, u32]
+    L.fa_window_workspace_bytes.restype = i64
+    L.fa_window_capacity_bytes.argtypes = [i64, i64, i64, i64, i64, i64, cint, u32]
+    L.fa_window_capacity_bytes.restype = i64
+    L.fa_window_device.argtypes = [vp, i64, vp, vp, i64, i64, vp, i64, i64, i64, cint, u32, vp, i64, vp, i64, vp, vp, pi64, vp]
+    L.fa_window_device.restype = cint
     L.fa_set_encode_md5.argtypes = [cint]
     L.fa_set_encode_md5.restype = cint
     L.fa_profile_enable.argtypes = [cint]

@@ -729,6 +729,96 @@ class FlacArray:
             self._resident = dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), index=None)
         self._st = new
 
+    def _window_on_device(self, first, last, streams, level, verify, what):
+        """What window and trim share: the argument and layout checks, then window_flac_device on the resident store or
+        an upload.  Returns (new _Store, its resident dict or None)."""
+        from .libflacarray import _encode_verify_default, _window_args, window_flac_device
+
+        st = self._st
+        if st.global_shape != st.grid:
+            raise NotImplementedError(f"{what} is not supported for a store that is one part of a distributed array")
+        first, last, B, idx = _window_args(st.count, st.samples, first, last, streams, level)
+        n = last - first
+        pick = lambda a: a if (a is None or idx is None) else np.asarray(a).reshape(-1)[idx]  # noqa: E731
+        new_shape = (tuple(st.shape[:-1]) + (n,)) if idx is None else (int(idx.size), n)
+        if idx is not None and idx.size == 0:
+            empty = np.zeros(0, dtype=np.int64)
+            return _Store.build(new_shape, None, st.dtype, np.zeros(0, dtype=np.uint8), empty, empty.copy(), pick(st.offsets), pick(st.gains)), None
+        _, _, _, bs, own = self._frame_index_layout()
+        if own is None:
+            raise ValueError("the store's stream index does not fit its compressed bytes")
+        if not own:
+            raise ValueError(f"{what} needs streams written by this library (a SEEKTABLE with one point per frame): reindex() adopts a "
+                             "libFLAC-written store first")
+        if np.any(bs != B):
+            raise ValueError(f"level {level} has block size {B}, the store's streams have {int(bs[bs != B][0])}: {what} at the store's level")
+        if verify is None:
+            verify = _encode_verify_default()
+        res = self._resident
+        _, comp, starts, nbytes = self._device_store()
+        # (a resident result keeps an exact-size blob, as append does; a host result only copies the bytes back)
+        comp2, starts2, nbytes2 = window_flac_device(comp, starts, nbytes, st.samples, first, last, streams=idx, level=level, is_int64=st.wide,
+                                                     verify=verify, compact=res is not None)
+        ishape = np.shape(st.starts) if idx is None else (int(idx.size),)
+        new = _Store.build(new_shape, None, st.dtype, comp2.cpu().numpy(), starts2.cpu().numpy().reshape(ishape),
+                           nbytes2.cpu().numpy().reshape(ishape), pick(st.offsets), pick(st.gains), st.dist)
+        if res is None:
+            return new, None
+        import torch
+
+        sel = lambda t: t if (t is None or idx is None) else t[torch.from_numpy(idx).to(t.device)]  # noqa: E731
+        return new, dict(res, compressed=comp2, starts=starts2.reshape(-1), nbytes=nbytes2.reshape(-1), offsets=sel(res["offsets"]),
+                         gains=sel(res["gains"]), index=None)
+
+    def window(self, first=0, last=None, streams=None, level=5, verify=None, md5=False):
+        """Samples [first, last) of every stream, or of the streams named, as a NEW FlacArray -- a compressed store, not a
+        decoded array (addition to the reference API).  This array is not modified.
+
+        `streams=None`: the result has shape leading_shape + (last - first,) (a 1-D array stays 1-D).  Otherwise `streams`
+        is a 1-D integer array of flat C-order stream indices (an index out of range or named twice raises ValueError)
+        and the result has shape (len(streams), last - first), rows in the order asked; an empty `streams` gives an empty
+        store of shape (0, last - first).  `stream_offsets` / `stream_gains` are those of the picked streams, unchanged.
+        0 <= first < last <= stream_size, else ValueError (an empty window is refused: there is no zero-sample stream).
+
+        Integer arrays: the result is byte for byte from_array(x[idx, first:last], level=level) with x the decoded array
+        -- `compressed`, `stream_starts` and `stream_nbytes` -- after any sequence of append, overwrite, trim and window,
+        provided `level` is the level the store was written at (a level of another block size raises ValueError).  Float
+        arrays: the integer encode of the quantised integers of the window; the decoded floats equal
+        to_array()[idx, first:last] bit for bit.
+
+        When `first` is a multiple of the block size (4096 samples at levels 3-8, 1152 at 0-2) no kept frame is decoded:
+        the frames are copied with their numbers lowered and the seek table rebuilt on the device, and only a `last` that
+        falls inside a frame has that one frame decoded and encoded again (window_flac_device).  Any other `first` moves
+        every frame boundary and COSTS A DECODE PLUS AN ENCODE of the window, done in row chunks of bounded memory.
+
+        A stream whose window is the whole stream is copied verbatim (pure stream selection: a signed stream keeps its
+        signature); every other stream comes out UNSIGNED, and `md5=True` is the call followed by sign().  `verify`:
+        frame_status of the result must be all zero and the re-encoded last frame must decode to the old samples, else
+        RuntimeError (None = the default of set_encode_verify).  The result is resident when this array is (an
+        exact-size blob), a host store otherwise.  Streams without this library's SEEKTABLE raise ValueError -- reindex()
+        adopts such a store first; a store assembled by `dist` raises NotImplementedError; a seek table whose offsets
+        are out of order raises RuntimeError."""
+        st = self._st
+        new, res = self._window_on_device(first, last, streams, level, verify, "window")
+        out = FlacArray._assemble(new.shape, None, st.dtype, new.blob, new.starts, new.nbytes_per_stream, new.offsets, new.gains)
+        out._resident = res
+        return out.sign() if (md5 and new.count) else out
+
+    def trim(self, first=0, last=None, level=5, verify=None, md5=False):
+        """Keep samples [first, last) of every stream, in place; returns self (addition to the reference API): what
+        window(first, last) returns becomes this array's store -- "keep the last hour" of an array fed by append, without a
+        decoded copy and, for a `first` on a frame boundary, without an encode.  Contract, cost, signatures and errors are
+        window's.  The store is replaced, not changed: a FlacArray(self) copy made before still holds the old one.  A
+        resident array stays resident, with an exact-size blob, and its decode index is closed and rebuilt on next use."""
+        new, res = self._window_on_device(first, last, None, level, verify, "trim")
+        old = self._resident
+        if old is not None and old.get("index") is not None:
+            old["index"].close()
+        if old is not None:
+            self._resident = res
+        self._st = new
+        return self.sign() if md5 else self
+
     def _device_store(self, scale=False):
         """(device, compressed, starts, nbytes) for a pass over the whole store: the resident tensors, or an upload.
         `scale`: followed by the offsets and gains (None for an integer store)."""

@@ -42,6 +42,7 @@
 #include "reduce_kernels.hpp"
 #include "scrub_kernels.hpp"
 #include "reindex_kernels.hpp"
+#include "window_kernels.hpp"
 
 namespace {
 
@@ -2596,6 +2597,156 @@ int fa_reindex_device(const unsigned char* d_old, int64_t n_old_bytes, const int
     hipLaunchKernelGGL(reindex_kernel, dim3((unsigned)(n_stream * parts)), dim3(256), 0, st, a);
     FA_HIP_TRY(hipGetLastError());
     FA_HIP_TRY(hipStreamSynchronize(st));  // (the tables are freed on return, the scratch is the next call's)
+    *h_total_bytes = back.total;
+    return FA_ERROR_NONE;
+}
+
+// ---- window (window_kernels.hpp, K14): the kept frames renumbered downwards, a cut inside a frame re-encoded ----------
+// Workspace layout (256-byte aligned regions): the picked streams' starts | nbytes, the output row of every stream, the
+// error word and total; with a tail (last inside an old frame) the decoded (m, r) image, the encode's blob (its capacity),
+// its starts | nbytes and the encode's own workspace.
+struct WindowPlan {
+    int64_t B, nf_old, f0, nk, nchk, nf_new, r, enc_cap, enc_ws;
+    bool tail, whole;
+    size_t off_sub, off_slot, off_small, off_img, off_blob, off_idx, off_ws, total;
+};
+static int make_window_plan(int nch, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t last, uint32_t level,
+                            WindowPlan* pl) {
+    if (nch != 1 && nch != 2) return FA_ERROR_CONVERT_TYPE;
+    FramePlan old;
+    const int rc = make_frame_plan(n_stream, stream_size, level, nch, &old);
+    if (rc && rc != FA_ERROR_ENCODE_PROCESS) return rc;  // (the limits were the old store's own encode's to refuse)
+    if (m < 0 || m > n_stream) return FA_ERROR_ZERO_NSTREAM;
+    if (first < 0 || last > stream_size || last <= first) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    pl->B = old.B;
+    pl->nf_old = old.nf;
+    if (first % pl->B) return FA_ERROR_DECODE_SAMPLE_RANGE;  // every frame boundary moves: nothing to copy, the caller encodes
+    const int64_t n = last - first;
+    pl->f0 = first / pl->B;
+    pl->whole = (first == 0 && last == stream_size);
+    if (last == stream_size) {  // the old last frame, short or not, is one more kept frame
+        pl->nk = pl->nf_old - pl->f0;
+        pl->r = 0;
+    } else {
+        pl->nk = n / pl->B;
+        pl->r = n % pl->B;
+    }
+    pl->tail = pl->r != 0;
+    pl->nf_new = pl->nk + (pl->tail ? 1 : 0);
+    pl->nchk = pl->whole ? 1 : pl->nf_new;
+    pl->enc_cap = pl->enc_ws = 0;
+    if (pl->tail && m > 0) {
+        FramePlan enc;  // the encode of the (m, r) image: one short frame per stream
+        if (make_frame_plan(m, pl->r, level, nch, &enc) != FA_ERROR_NONE) return FA_ERROR_ENCODE_INIT;
+        pl->enc_cap = enc.capacity;
+        pl->enc_ws = single_pass_workspace_for(m, pl->r, level, nch);
+    }
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t o = 0;
+    pl->off_sub = o; o += up((size_t)m * 16);
+    pl->off_slot = o; o += up((size_t)n_stream * 4);
+    pl->off_small = o; o += 256;
+    pl->off_img = o; o += pl->tail ? up((size_t)m * (size_t)pl->r * 4 * (size_t)nch) : 0;
+    pl->off_blob = o; o += pl->tail ? up((size_t)pl->enc_cap + 64) : 0;
+    pl->off_idx = o; o += pl->tail ? up((size_t)m * 16) : 0;
+    pl->off_ws = o; o += up((size_t)pl->enc_ws);
+    pl->total = o;
+    return FA_ERROR_NONE;
+}
+
+int64_t fa_window_workspace_bytes(int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t last, int channels, uint32_t level) {
+    WindowPlan pl;
+    return make_window_plan(channels, n_stream, stream_size, m, first, last, level, &pl) ? -1 : (int64_t)pl.total;
+}
+// a picked stream's header and kept frames only shrink; what can grow is the re-encoded tail frame, bounded by its encode
+int64_t fa_window_capacity_bytes(int64_t n_picked_bytes, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t last, int channels,
+                                 uint32_t level) {
+    WindowPlan pl;
+    if (n_picked_bytes < 0 || make_window_plan(channels, n_stream, stream_size, m, first, last, level, &pl)) return -1;
+    return n_picked_bytes + pl.enc_cap + 6 * m + 64;
+}
+
+int fa_window_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes, int64_t n_stream,
+                     int64_t stream_size, const int64_t* d_stream_index, int64_t m, int64_t first, int64_t last, int channels, uint32_t level,
+                     void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
+                     int64_t* d_nbytes, int64_t* h_total_bytes, void* stream) {
+    FA_API_LOCK;
+    if (!h_total_bytes) return FA_ERROR_ALLOC;
+    *h_total_bytes = 0;
+    if (!d_stream_index && m != n_stream && m != 0) return FA_ERROR_ZERO_NSTREAM;
+    WindowPlan pl;
+    int rc = make_window_plan(channels, n_stream, stream_size, m, first, last, level, &pl);
+    if (rc) return rc;
+    if (m == 0) return FA_ERROR_NONE;  // an empty store: nothing to launch
+    if (n_old_bytes <= 0 || !d_old || !d_old_starts || !d_old_nbytes || !d_starts || !d_nbytes) return FA_ERROR_DECODE_INIT;
+    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
+    if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
+    // (the copy reads its sources in aligned 16-byte blocks)
+    if ((reinterpret_cast<uintptr_t>(d_old) & 15) || (reinterpret_cast<uintptr_t>(d_workspace) & 15)) return FA_ERROR_ENCODE_INIT;
+    const int nch = channels;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* ws = reinterpret_cast<char*>(d_workspace);
+    WindowArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.old = d_old; a.old_bytes = n_old_bytes; a.old_starts = d_old_starts; a.old_nbytes = d_old_nbytes;
+    a.sidx = d_stream_index;
+    a.slot = reinterpret_cast<int32_t*>(ws + pl.off_slot);
+    a.sub_starts = reinterpret_cast<int64_t*>(ws + pl.off_sub);
+    a.sub_nbytes = a.sub_starts + m;
+    a.starts = d_starts; a.nbytes = d_nbytes; a.out = d_bytes;
+    a.err = reinterpret_cast<int*>(ws + pl.off_small);
+    a.n_stream = n_stream; a.m = m; a.size_old = stream_size; a.size_new = last - first;
+    a.f0 = pl.f0; a.nk = pl.nk; a.nchk = pl.nchk; a.nf_old = pl.nf_old; a.nf_new = pl.nf_new;
+    a.B = (int32_t)pl.B; a.nch = nch; a.tail = pl.tail ? 1 : 0; a.whole = pl.whole ? 1 : 0;
+    // 0. the stream index, the layout of every picked stream, and every seek offset the copy or the tail decode follows
+    const int64_t nt = m * pl.nchk;
+    if (nt >= (1LL << 31) * 256) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
+    FA_HIP_TRY(hipMemsetAsync(a.sub_starts, 0, (size_t)m * 16, st));
+    if (d_stream_index) {
+        FA_HIP_TRY(hipMemsetAsync(a.slot, 0xFF, (size_t)n_stream * 4, st));
+    }
+    hipLaunchKernelGGL(window_check_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, a);
+    {
+        int h_err = 0;
+        FA_HIP_TRY(hipMemcpyAsync(&h_err, a.err, sizeof h_err, hipMemcpyDeviceToHost, st));
+        FA_HIP_TRY(hipStreamSynchronize(st));
+        FA_HIP_TRY(hipGetLastError());
+        if (h_err & kWindowBadIndex) return FA_ERROR_ZERO_NSTREAM;
+        if (h_err & kWindowBadLayout) return FA_ERROR_DECODE_INIT;
+        if (h_err) return FA_ERROR_DECODE_SEEK;
+    }
+    // 1. the tail: old frame f0 + nk decoded up to the cut, encoded again as one short frame per stream, numbered 0
+    if (pl.tail) {
+        char* img = ws + pl.off_img;
+        const int64_t lo = (pl.f0 + pl.nk) * pl.B;
+        rc = decode_span(nch, d_old, n_old_bytes, a.sub_starts, a.sub_nbytes, m, stream_size, lo, last, img, stream);
+        if (rc) return rc;
+        unsigned char* blob = reinterpret_cast<unsigned char*>(ws + pl.off_blob);
+        int64_t* e_idx = reinterpret_cast<int64_t*>(ws + pl.off_idx);
+        int64_t enc_total = 0;
+        rc = encode_image(nch, img, m, pl.r, level, ws + pl.off_ws, pl.enc_ws, blob, pl.enc_cap, e_idx, &enc_total, stream);
+        if (rc) return rc;
+        a.enc = blob; a.enc_bytes = enc_total; a.enc_starts = e_idx; a.enc_nbytes = e_idx + m;
+    }
+    // 2. sizes, starts (one wait: the error word and the total), then the copy
+    int64_t* d_total = reinterpret_cast<int64_t*>(ws + pl.off_small + 8);
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
+    hipLaunchKernelGGL(window_size_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_nbytes, m, d_starts, d_total);
+    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
+    FA_HIP_TRY(hipMemcpyAsync(&back, a.err, sizeof back, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (back.err) return FA_ERROR_DECODE_INIT;  // (the tail encode's index)
+    if (back.total > capacity_bytes) return FA_ERROR_ALLOC;
+    // workgroups per stream: ~64 KB of the result each (at most 1024, and a grid of fewer than 2^23 workgroups)
+    int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, back.total / m / 65536));
+    while (parts > 1 && m * parts >= (1LL << 23)) parts >>= 1;
+    if (m * parts >= (1LL << 23)) return FA_ERROR_ALLOC;
+    a.parts = (int32_t)parts;
+    hipLaunchKernelGGL(window_kernel, dim3((unsigned)(m * parts)), dim3(256), 0, st, a);
+    FA_HIP_TRY(hipGetLastError());
     *h_total_bytes = back.total;
     return FA_ERROR_NONE;
 }

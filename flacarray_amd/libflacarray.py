@@ -1837,3 +1837,141 @@ def reindex_flac_device(compressed, starts, nbytes, stream_size, is_int64=False,
             raise RuntimeError(f"Reindexing failed: {bad.shape[0]} frame(s) of the result do not check (first: stream {s_bad}, frame {f_bad}, "
                                f"status {int(status.reshape(n_stream, -1)[s_bad, f_bad])}); verify=False adopts the store as it is, for salvage")
     return out
+
+
+def _window_args(n_stream, stream_size, first, last, streams, level):
+    """The argument checks of a window (ValueError, before anything touches the GPU).  Returns (first, last, block size,
+    stream indices as an int64 numpy array or None)."""
+    stream_size = int(stream_size)
+    if stream_size <= 0:
+        raise ValueError("You must specify the non-zero stream size")
+    if level < 0 or level > 8:
+        raise ValueError("FLAC only supports compression levels 0-8")
+    first = int(first)
+    last = stream_size if last is None else int(last)
+    if first < 0 or last > stream_size or last <= first:
+        raise ValueError(f"samples [{first}, {last}) are not a non-empty range inside streams of {stream_size} samples "
+                         "(there is no zero-sample stream to write)")
+    return first, last, (1152 if level <= 2 else 4096), _stream_indices(streams, n_stream)
+
+
+def window_flac_device(compressed, starts, nbytes, stream_size, first=0, last=None, streams=None, level=5, is_int64=False, verify=False,
+                       compact=False, max_temp_bytes=None):
+    """Cut samples [first, last) of every stream of a device-resident store, or of the streams that `streams` names
+    (1-D flat C-order indices, no repeats; the new streams come in that order), out as a NEW store: returns its
+    (compressed, starts, nbytes), all on the device, the arguments left as they are.  starts / nbytes have the shape of
+    `starts` for streams=None and (len(streams),) otherwise; an empty `streams` gives an empty store.
+
+    The store must have this library's layout (one SEEKTABLE point per frame; reindex_flac_device adopts others) and
+    `level` the level it was written at (its block size B is checked against the streams' STREAMINFO).  For streams of
+    integers the result is then byte for byte encode_flac_device(x[idx, first:last], level) with x the decoded array
+    (for a float store: of the quantised integers), after any sequence of appends, overwrites and windows.
+
+    first % B == 0 (fa_window_device, include/flacarray_hip.h): no sample of a frame that is kept whole is decoded.  The
+    frames first / B, ... are copied with their numbers lowered (number field, CRC-8, CRC-16 by its linear identity), the
+    seek table is rebuilt from the old one, and only where `last` falls inside an old frame is that one frame decoded up to
+    the cut and encoded again as the short last frame.  first == 0 renumbers nothing.  A window that is the whole stream
+    copies each picked stream verbatim -- pure stream selection, a signed stream keeps its signature; every other window
+    comes out with a zero STREAMINFO MD5.
+
+    first % B != 0: every frame boundary moves, so every frame changes, and this route COSTS A DECODE PLUS AN ENCODE of
+    the window: the picked streams are decoded on [first, last) in row chunks of at most `max_temp_bytes` (default
+    256 MiB, at least one row) and each chunk is encoded with encode_flac_device; streams are independent, so the
+    pieces put back to back are byte for byte the one-shot encode, and the extra memory is one chunk beside the result
+    (at 4096 x 2^20 and the default chunk size about twice the time of one decode plus one encode, for a seventh of their
+    memory: profiles/window.md).
+
+    `compressed` is a view of a buffer sized for the picked streams plus the worst case of the re-encoded frame;
+    `compact=True` returns an exact-size copy instead.  `verify=True`: frame_status_device over the RESULT must be all
+    zero (every frame carries its new number, a clean CRC-8 and CRC-16), and the re-encoded last frame is decoded from the
+    result and compared with the old samples it was made from (the unaligned route compares every chunk's encode with
+    its input); RuntimeError otherwise.
+
+    ValueError: an empty or outside range, a bad stream index, a level outside 0-8, or streams that are not this
+    library's for the call's block size, channel count (is_int64: two) and stream size.  RuntimeError: a seek table
+    whose offsets are not ordered inside the stream body or a frame shorter than its header plus CRC-16 (refused by the
+    check kernel's error word before anything is read through such an offset)."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64 or starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes should be int64 tensors of one shape")
+    n_stream = int(np.prod(starts.shape))
+    first, last, B, idx = _window_args(n_stream, stream_size, first, last, streams, level)
+    stream_size = int(stream_size)
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("window_flac_device needs compressed, starts and nbytes on the same GPU")
+    m = n_stream if idx is None else int(idx.size)
+    out_shape = tuple(starts.shape) if idx is None else (m,)
+    if m == 0:
+        return compressed.new_empty(0), starts.new_empty(out_shape), nbytes.new_empty(out_shape)
+    n = last - first
+    nch = 2 if is_int64 else 1
+    L = _lib.lib()
+    with _on_device(dev):
+        comp = compressed.contiguous()
+        if comp.data_ptr() & 15:  # (the copy reads its source in aligned 16-byte blocks)
+            comp = comp.clone()
+        st, nb = starts.reshape(-1).contiguous(), nbytes.reshape(-1).contiguous()
+        d_idx = None if idx is None else torch.from_numpy(idx).to(dev)
+        rows = slice(None) if d_idx is None else d_idx
+        if first % B:
+            # unaligned: decode and encode, a chunk of rows at a time
+            cap = (256 << 20) if max_temp_bytes is None else int(max_temp_bytes)
+            per = max(1, cap // (n * 4 * nch))
+            sub_st, sub_nb = st[rows].contiguous(), nb[rows].contiguous()
+            blobs, sizes = [], []
+            for r0 in range(0, m, per):
+                x = decode_flac_device(comp, sub_st[r0 : r0 + per], sub_nb[r0 : r0 + per], stream_size, first, last, is_int64=is_int64)
+                # (compact: a piece must not keep its worst-case buffer alive while the others are made)
+                b, _, nbs = encode_flac_device(x, level=level, compact=True, verify=bool(verify), md5=False)
+                blobs.append(b)
+                sizes.append(nbs.reshape(-1))
+                del x
+            nbytes2 = torch.cat(sizes)
+            starts2 = torch.cumsum(nbytes2, 0) - nbytes2
+            blob = torch.cat(blobs) if len(blobs) > 1 else blobs[0]  # (exact-size either way)
+        else:
+            picked = int(nb[rows].sum().item())
+            ws_bytes = L.fa_window_workspace_bytes(n_stream, stream_size, m, first, last, nch, level)
+            cap = L.fa_window_capacity_bytes(max(picked, 0), n_stream, stream_size, m, first, last, nch, level)
+            if ws_bytes < 0 or cap < 0:
+                raise RuntimeError("Windowing failed: invalid geometry")
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            buf = torch.empty(cap, dtype=torch.uint8, device=dev)
+            index = torch.empty(2 * m, dtype=torch.int64, device=dev)
+            total = ctypes.c_int64(0)
+            errcode = L.fa_window_device(_dp(comp), comp.numel(), _dp(st), _dp(nb), n_stream, stream_size, _dp(d_idx), m, first, last, nch, level,
+                                         _dp(ws), ws.numel(), _dp(buf), cap, _dp(index[:m]), _dp(index[m:]), ctypes.byref(total), _stream_ptr())
+            if errcode == 8192:  # FA_ERROR_DECODE_INIT
+                raise ValueError(f"Windowing needs streams written by this library (a SEEKTABLE with one point per frame; reindex() adopts "
+                                 f"other stores) with the block size of level {level}, {nch} channel(s) and {stream_size} samples")
+            if errcode == 1 << 18:  # FA_ERROR_DECODE_SEEK
+                raise RuntimeError("Windowing failed: a seek table's offsets are not ordered inside the stream body, or a frame is shorter "
+                                   "than its header plus the CRC-16")
+            if errcode != 0:
+                raise RuntimeError(f"Windowing failed, return code = {errcode}")
+            blob = buf[: total.value]
+            if compact:
+                blob = blob.clone()
+                del buf
+            starts2, nbytes2 = index[:m], index[m:]
+        out = (blob, starts2.reshape(out_shape), nbytes2.reshape(out_shape))
+        if verify:
+            status = frame_status_device(out[0], starts2, nbytes2, n, is_int64=is_int64, block_size=B)
+            bad = torch.nonzero(status.reshape(m, -1))
+            if bad.numel():
+                s_bad, f_bad = (int(v) for v in bad[0])
+                raise RuntimeError(f"Windowing failed: {bad.shape[0]} frame(s) of the result do not check (first: stream {s_bad}, frame {f_bad}, "
+                                   f"status {int(status.reshape(m, -1)[s_bad, f_bad])})")
+            r = n % B
+            if first % B == 0 and r and last != stream_size:  # the re-encoded last frame against the old samples
+                got = decode_flac_device(out[0], starts2, nbytes2, n, n - r, n, is_int64=is_int64, verify=True).reshape(m, -1)
+                want = decode_flac_device(comp, st[rows].contiguous(), nb[rows].contiguous(), stream_size, last - r, last,
+                                          is_int64=is_int64).reshape(m, -1)
+                diff = got != want
+                if bool(diff.any()):
+                    hit = diff.any(dim=1)
+                    _raise_on_mismatch(torch.where(hit, diff.int().argmax(dim=1) + (n - r), torch.full_like(hit, -1, dtype=torch.int64)))
+    return out

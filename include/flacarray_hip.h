@@ -484,6 +484,41 @@ int fa_reindex_device(const unsigned char* d_old, int64_t n_old_bytes, const int
                       int64_t n_stream, int64_t stream_size, int n_channels, unsigned char* d_bytes, int64_t capacity_bytes,
                       int64_t* d_starts, int64_t* d_nbytes, int64_t* h_total_bytes, void* stream);
 
+/* Window: cut samples [first, last) of m streams of a store out as a NEW store of m streams, without re-encoding the
+ * frames that are kept whole (window_kernels.hpp, K14).  `first` must be a multiple of the block size B of `level`
+ * (FA_ERROR_DECODE_SAMPLE_RANGE otherwise, as for first < 0, last > stream_size and last <= first: with an unaligned
+ * first every frame boundary moves and the window has to be decoded and encoded, which is the caller's to do).  The
+ * frames f0 = first / B, f0 + 1, ... are copied with their numbers lowered by f0 (the UTF-8 number field, the header
+ * CRC-8, and the CRC-16 through its linear identity: no pass over a payload), the seek table is rebuilt in closed form
+ * from the old one, and the stream header is written for last - first samples with a zero MD5.  Where last falls inside
+ * an old frame (and is not the old end) that one frame is decoded up to the cut and encoded again as a short last
+ * frame; where last == stream_size the old last frame is one more kept frame.  For integer stores the result is byte
+ * for byte the encode of the decoded window at `level`, provided that is the level the store was written at.  Two
+ * shortcuts: first == 0 renumbers nothing (the kept points and frames are copied as they are); first == 0 && last ==
+ * stream_size copies every picked stream verbatim, its STREAMINFO MD5 included (pure stream selection).
+ * d_stream_index: m flat stream indices (device), the output order; NULL: all streams (m == n_stream).  An index out of
+ * range or named twice gives FA_ERROR_ZERO_NSTREAM.  m == 0 returns FA_ERROR_NONE with a total of 0 and launches nothing.
+ * channels: 1 for int32 / float32 arrays, 2 for int64 / float64 (no sample format enters the copy; the tail decode and
+ * encode pick their path from it).  Every picked stream must be one this library wrote for the call's block size,
+ * channel count and stream size, with one seek point per frame (FA_ERROR_DECODE_INIT otherwise; fa_reindex_device
+ * adopts other stores), and every seek offset of the frames the call follows must be ordered inside the stream's body
+ * and leave each frame its own header plus the CRC-16, at least 13 bytes (FA_ERROR_DECODE_SEEK otherwise).  Both are
+ * checked by one kernel before anything is decoded or copied, and on every error nothing is written to d_bytes.
+ * d_old and d_workspace must be 16-byte aligned (FA_ERROR_ENCODE_INIT); d_old is unchanged and d_bytes must not overlap
+ * it.  fa_window_workspace_bytes() is the workspace the call needs; fa_window_capacity_bytes(n_picked_bytes, ...) a
+ * capacity that always suffices, given the bytes of the picked streams or any upper bound of them (the whole old blob,
+ * say): a kept frame never grows, so the bound is those bytes plus the worst case of the re-encoded frame; a smaller
+ * buffer gives FA_ERROR_ALLOC if the result does not fit.  Both return -1 for arguments the call refuses.  The new
+ * streams lie back to back from 0 in the order asked, d_starts / d_nbytes [m] are their index, *h_total_bytes the bytes
+ * used; no byte of d_bytes from there on is written.  All work is issued on `stream`; the copy is not waited for. */
+int64_t fa_window_workspace_bytes(int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t last, int channels, uint32_t level);
+int64_t fa_window_capacity_bytes(int64_t n_picked_bytes, int64_t n_stream, int64_t stream_size, int64_t m, int64_t first, int64_t last,
+                                 int channels, uint32_t level);
+int fa_window_device(const unsigned char* d_old, int64_t n_old_bytes, const int64_t* d_old_starts, const int64_t* d_old_nbytes, int64_t n_stream,
+                     int64_t stream_size, const int64_t* d_stream_index, int64_t m, int64_t first, int64_t last, int channels, uint32_t level,
+                     void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
+                     int64_t* d_nbytes, int64_t* h_total_bytes, void* stream);
+
 /* Batched random access: slice i is samples [first[i], first[i]+count[i]) of stream
  * slice_stream[i]; its samples are written at element offset out_offset[i] of the output.
  * The four slice arrays are HOST arrays of length n_slices.  The reference needs one
