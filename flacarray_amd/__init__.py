@@ -25,6 +25,7 @@ from .libflacarray import (
     float32_to_int32_device,
     float64_to_int64_device,
     frame_status_device,
+    join_flac_device,
     md5_device,
     overwrite_flac_device,
     reduce_flac_device,
@@ -52,6 +53,7 @@ __all__ = [
     "overwrite_flac_device",
     "reindex_flac_device",
     "window_flac_device",
+    "join_flac_device",
     "array_compress",
     "array_decompress",
     "array_decompress_slice",

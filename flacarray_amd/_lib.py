@@ -83,6 +83,9 @@ SYMBOLS = [
     "fa_window_workspace_bytes",
     "fa_window_capacity_bytes",
     "fa_window_device",
+    "fa_join_workspace_bytes",
+    "fa_join_capacity_bytes",
+    "fa_join_device",
     "fa_encode_f32_host",
     "fa_encode_f64_host",
     "fa_decode_f32_host",
@@ -259,6 +262,12 @@ def lib():
     L.fa_window_capacity_bytes.restype = i64
     L.fa_window_device.argtypes = [vp, i64, vp, vp, i64, i64, vp, i64, i64, i64, cint, u32, vp, i64, vp, i64, vp, vp, pi64, vp]
     L.fa_window_device.restype = cint
+    L.fa_join_workspace_bytes.argtypes = [i64, i64, pi64, cint, u32]
+    L.fa_join_workspace_bytes.restype = i64
+    L.fa_join_capacity_bytes.argtypes = [i64, pi64, i64, pi64, cint, u32]
+    L.fa_join_capacity_bytes.restype = i64
+    L.fa_join_device.argtypes = [i64, vp, pi64, vp, vp, pi64, i64, cint, u32, vp, i64, vp, i64, vp, vp, pi64, vp]
+    L.fa_join_device.restype = cint
     L.fa_set_encode_md5.argtypes = [cint]
     L.fa_set_encode_md5.restype = cint
     L.fa_profile_enable.argtypes = [cint]

@@ -819,6 +819,161 @@ class FlacArray:
         self._st = new
         return self.sign() if md5 else self
 
+    @classmethod
+    def _stack(cls, arrays, md5):
+        """concatenate(axis=0): the parts' streams verbatim in order, stream_starts shifted by the bytes in front."""
+        st0 = arrays[0]._st
+        if len(st0.shape) < 2:
+            raise ValueError("a 1-D array has the sample axis only: concatenate it with axis=-1")
+        for a in arrays:
+            st = a._st
+            if st.global_shape != st.grid:
+                raise NotImplementedError("concatenate is not supported for a store that is one part of a distributed array")
+            if st.dtype != st0.dtype:
+                raise ValueError(f"the parts differ in dtype ({st.dtype} beside {st0.dtype})")
+            if len(st.shape) != len(st0.shape) or st.shape[1:] != st0.shape[1:]:
+                raise ValueError(f"axis 0 joins arrays of one stream_size and equal shape[1:], got {st.shape} beside {st0.shape}")
+        sizes = [a._st.blob_bytes for a in arrays]
+        fronts = np.cumsum([0] + sizes[:-1])
+        lead = lambda a, v: np.asarray(v).reshape(a._st.lead)  # noqa: E731
+        blob = np.concatenate([np.asarray(a._st.blob, dtype=np.uint8) for a in arrays])
+        starts = np.concatenate([lead(a, a._st.starts).astype(np.int64) + int(f) for a, f in zip(arrays, fronts)], axis=0)
+        nbytes = np.concatenate([lead(a, a._st.nbytes_per_stream).astype(np.int64) for a in arrays], axis=0)
+        offsets = gains = None
+        if st0.offsets is not None:
+            offsets = np.concatenate([lead(a, a._st.offsets) for a in arrays], axis=0)
+            gains = np.concatenate([lead(a, a._st.gains) for a in arrays], axis=0)
+        shape = (sum(a._st.shape[0] for a in arrays),) + tuple(st0.shape[1:])
+        out = cls._assemble(shape, None, st0.dtype, blob, starts, nbytes, offsets, gains)
+        res0 = arrays[0]._resident
+        if res0 is not None:
+            import torch
+
+            dev = res0["device"]
+            parts = [a._device_store(scale=True) for a in arrays]  # (resident tensors, or an upload)
+            cat = lambda k: torch.cat([p[k].to(dev) for p in parts])  # noqa: E731
+            front = torch.from_numpy(np.asarray(fronts, dtype=np.int64)).to(dev)
+            out._resident = {
+                "device": dev, "compressed": cat(1), "starts": torch.cat([p[2].to(dev) + front[i] for i, p in enumerate(parts)]),
+                "nbytes": cat(3), "offsets": None if offsets is None else cat(4), "gains": None if gains is None else cat(5),
+            }
+        return out.sign() if md5 else out
+
+    @classmethod
+    def concatenate(cls, arrays, axis=-1, level=5, verify=None, md5=False):
+        """Join FlacArrays into a NEW FlacArray without re-encoding them (addition to the reference API).  No input is
+        modified.
+
+        `axis=-1`, the sample axis: all arrays have one dtype and one leading shape, lengths may differ, 1-D arrays stay
+        1-D.  Integer arrays: with x_i the decoded arrays, `compressed`, `stream_starts` and `stream_nbytes` are byte for
+        byte those of from_array(np.concatenate(x_i, axis=-1), level=level), for any number of parts and any lengths,
+        after any sequence of append, overwrite, trim, window, concatenate and extend -- provided `level` is the level
+        the stores were written at (a block size other than that of `level` in any part raises ValueError).  Float
+        arrays: `stream_offsets` and `stream_gains` of all parts must be equal bit for bit, else ValueError (the parts
+        were quantised differently: decode them and compress the concatenation again); the result is the integer encode
+        of the concatenated quantised integers, its decoded floats are np.concatenate of the parts' to_array() bit for
+        bit, and offsets and gains carry over unchanged.  Nothing is re-quantised, hence no `quanta` / `precision`.
+
+        When every part but the last is a whole number of blocks long (4096 samples at levels 3-8, 1152 at 0-2) no
+        sample is decoded and nothing is encoded: the frames are copied with their numbers raised and the seek table is
+        rebuilt on the device (join_flac_device), and the first part moves at copy speed.  Any other split COSTS A DECODE
+        PLUS AN ENCODE of everything behind the first unaligned boundary, done in row chunks of bounded memory, AND IS
+        SLOWER than decoding those parts and appending them in one go (profiles/join.md).
+
+        A single part is returned as a verbatim copy, signature included.  Any result made from two or more parts
+        comes out UNSIGNED (STREAMINFO MD5 zero): a finished digest cannot be resumed; `md5=True` is the call followed
+        by sign(), explicit only.  `verify` (None = the default of set_encode_verify): frame_status of the RESULT must be
+        all zero -- every frame carries its new number, its block size, a clean CRC-8 and a clean CRC-16 -- else
+        RuntimeError; on the unaligned route the appended span is also verified as append(verify=True) does.
+
+        The result is resident when arrays[0] is (an exact-size blob), a host store otherwise; parts that are not
+        resident are uploaded for the call, and the host mirror is filled as append fills it.  Every part must have this
+        library's layout (`has_frame_index`), else ValueError -- reindex() adopts such a store first; a part of a `dist`
+        store raises NotImplementedError; an empty `arrays` raises ValueError.
+
+        `axis=0`, the first leading axis: the arrays have one dtype, one stream_size and equal shape[1:] (1-D arrays
+        raise ValueError: their only axis is the sample axis).  The streams are copied verbatim in order, with
+        `stream_starts` shifted by the bytes in front; offsets and gains are concatenated.  Every stream keeps its bytes
+        and therefore its signature, and layouts may differ between parts, since nothing is parsed.  `level` and `verify`
+        are ignored; `md5=True` signs afterwards."""
+        from .libflacarray import _encode_verify_default, _join_args, join_flac_device
+
+        arrays = list(arrays)
+        if not arrays:
+            raise ValueError("concatenate needs at least one array")
+        if not all(isinstance(a, FlacArray) for a in arrays):
+            raise ValueError("concatenate takes FlacArrays (append takes raw samples)")
+        st0 = arrays[0]._st
+        nd = len(st0.shape)
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
+            raise ValueError(f"axis {axis!r} is not an integer")
+        if axis == 0 and nd == 1:
+            raise ValueError("a 1-D array has the sample axis only: concatenate it with axis=-1")
+        if axis == 0 or (axis == -nd and nd > 1):
+            return cls._stack(arrays, md5)
+        if axis not in (-1, nd - 1):
+            raise ValueError(f"axis {axis} is neither the sample axis (-1) nor the first leading axis (0)")
+        for a in arrays:
+            st = a._st
+            if st.global_shape != st.grid:
+                raise NotImplementedError("concatenate is not supported for a store that is one part of a distributed array")
+            if st.dtype != st0.dtype:
+                raise ValueError(f"the parts differ in dtype ({st.dtype} beside {st0.dtype})")
+            if len(st.shape) != nd or st.shape[:-1] != st0.shape[:-1]:
+                raise ValueError(f"the parts differ in leading shape ({st.shape[:-1]} beside {st0.shape[:-1]})")
+        B, sizes, _ = _join_args([a._st.count for a in arrays], [a._st.samples for a in arrays], level)
+        if st0.offsets is not None:
+            ft = np.float64 if st0.wide else np.float32
+            bits = lambda v: np.ascontiguousarray(v, dtype=ft).tobytes()  # noqa: E731
+            if any(bits(a._st.offsets) != bits(st0.offsets) or bits(a._st.gains) != bits(st0.gains) for a in arrays[1:]):
+                raise ValueError("the parts were quantised differently (their stream_offsets / stream_gains are not equal bit for bit): "
+                                 "decode them and compress the concatenation again")
+        for a in arrays:
+            _, _, _, bs, own = a._frame_index_layout()
+            if own is None:
+                raise ValueError("a part's stream index does not fit its compressed bytes")
+            if not own:
+                raise ValueError("concatenate needs streams written by this library (a SEEKTABLE with one point per frame): reindex() adopts "
+                                 "a libFLAC-written store first")
+            if np.any(bs != B):
+                raise ValueError(f"level {level} has block size {B}, a part's streams have {int(bs[bs != B][0])}: concatenate at the "
+                                 "stores' level")
+        if verify is None:
+            verify = _encode_verify_default()
+        import torch
+
+        res0 = arrays[0]._resident
+        dev = res0["device"] if res0 is not None else torch.device("cuda", torch.cuda.current_device())
+        stores = []
+        for a in arrays:
+            _, comp, starts, nbytes = a._device_store()
+            stores.append((comp.to(dev), starts.to(dev), nbytes.to(dev), a._st.samples))
+        # (a resident result keeps an exact-size blob, as append does; a host result only copies the bytes back)
+        comp2, starts2, nbytes2 = join_flac_device(stores, level=level, is_int64=st0.wide, verify=verify, compact=res0 is not None)
+        ishape = np.shape(st0.starts)
+        out = cls._assemble(tuple(st0.shape[:-1]) + (sum(sizes),), None, st0.dtype, comp2.cpu().numpy(), starts2.cpu().numpy().reshape(ishape),
+                            nbytes2.cpu().numpy().reshape(ishape), copy.deepcopy(st0.offsets), copy.deepcopy(st0.gains))
+        if res0 is not None:
+            out._resident = {"device": dev, "compressed": comp2, "starts": starts2.reshape(-1), "nbytes": nbytes2.reshape(-1),
+                             "offsets": res0["offsets"], "gains": res0["gains"]}
+        return out.sign() if md5 else out
+
+    def extend(self, other, level=5, verify=None, md5=False):
+        """Extend every stream by the samples of another FlacArray, in place; returns self (addition to the reference
+        API): what concatenate([self, other], level=level) returns becomes this array's store -- append for data that
+        arrives compressed; with trim, a rolling store whose new data is never decoded.  Contract, cost, signatures and
+        errors are those of concatenate on the sample axis; `other` is not modified.  The store is replaced, not changed:
+        a FlacArray(self) copy made before still holds the old one.  The result is resident when this array is, with an
+        exact-size blob; its decode index is closed and rebuilt on next use.  When `verify` fails RuntimeError is raised
+        and both arrays stay as they were."""
+        new = FlacArray.concatenate([self, other], axis=-1, level=level, verify=verify, md5=md5)
+        old = self._resident
+        if old is not None and old.get("index") is not None:
+            old["index"].close()
+        self._resident = new._resident
+        self._st = new._st
+        return self
+
     def _device_store(self, scale=False):
         """(device, compressed, starts, nbytes) for a pass over the whole store: the resident tensors, or an upload.
         `scale`: followed by the offsets and gains (None for an integer store)."""

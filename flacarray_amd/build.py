@@ -21,6 +21,7 @@ DEPS = [
     os.path.join(_HERE, "csrc", "scrub_kernels.hpp"),
     os.path.join(_HERE, "csrc", "reindex_kernels.hpp"),
     os.path.join(_HERE, "csrc", "window_kernels.hpp"),
+    os.path.join(_HERE, "csrc", "join_kernels.hpp"),
     os.path.join(os.path.dirname(_HERE), "include", "flacarray_hip.h"),
 ]
 SRC_COMPACT = os.path.join(_HERE, "csrc", "compact_unit.hip")

@@ -43,6 +43,7 @@
 #include "scrub_kernels.hpp"
 #include "reindex_kernels.hpp"
 #include "window_kernels.hpp"
+#include "join_kernels.hpp"
 
 namespace {
 
@@ -2746,6 +2747,134 @@ int fa_window_device(const unsigned char* d_old, int64_t n_old_bytes, const int6
     if (m * parts >= (1LL << 23)) return FA_ERROR_ALLOC;
     a.parts = (int32_t)parts;
     hipLaunchKernelGGL(window_kernel, dim3((unsigned)(m * parts)), dim3(256), 0, st, a);
+    FA_HIP_TRY(hipGetLastError());
+    *h_total_bytes = back.total;
+    return FA_ERROR_NONE;
+}
+
+// ---- join (join_kernels.hpp, K15): the parts' frames behind one another, renumbered upwards ------------------------------
+// Workspace layout (256-byte aligned regions): the part descriptors, D_p(s) for every part and stream, the error word and
+// total.
+struct JoinPlan {
+    int64_t B, nf_new, size_new, growth_sum;
+    std::vector<int64_t> nf, base, growth;
+    bool whole;
+    size_t off_parts, off_D, off_small, total;
+};
+static int make_join_plan(int nch, int64_t n_parts, int64_t n_stream, const int64_t* sizes, uint32_t level, JoinPlan* pl) {
+    if (nch != 1 && nch != 2) return FA_ERROR_CONVERT_TYPE;
+    if (level > 8) return FA_ERROR_INVALID_LEVEL;
+    if (n_parts <= 0 || n_stream < 0) return FA_ERROR_ZERO_NSTREAM;
+    if (n_parts > kJoinMaxParts) return FA_ERROR_ENCODE_PROCESS;  // (an implementation limit: join in groups)
+    if (!sizes) return FA_ERROR_DECODE_INIT;
+    pl->B = level_params(level).blocksize;
+    pl->nf.resize((size_t)n_parts); pl->base.resize((size_t)n_parts); pl->growth.resize((size_t)n_parts);
+    int64_t total = 0;
+    for (int64_t p = 0; p < n_parts; ++p) {
+        if (sizes[p] <= 0) return FA_ERROR_ZERO_STREAMSIZE;
+        if (sizes[p] >= (1LL << 36) || (total += sizes[p]) >= (1LL << 36)) return FA_ERROR_DECODE_SAMPLE_RANGE;  // STREAMINFO holds 36 bits
+    }
+    total = 0;
+    pl->growth_sum = 0;
+    for (int64_t p = 0; p < n_parts; ++p) {
+        // every frame boundary behind an unaligned part moves: nothing to copy there, the caller decodes and encodes
+        if (total % pl->B) return FA_ERROR_DECODE_SAMPLE_RANGE;
+        pl->nf[(size_t)p] = (sizes[p] + pl->B - 1) / pl->B;
+        pl->base[(size_t)p] = total / pl->B;
+        pl->growth[(size_t)p] = append_growth(pl->base[(size_t)p], pl->nf[(size_t)p]);
+        pl->growth_sum += pl->growth[(size_t)p];
+        total += sizes[p];
+    }
+    pl->size_new = total;
+    pl->nf_new = pl->base[(size_t)n_parts - 1] + pl->nf[(size_t)n_parts - 1];
+    if (18 * pl->nf_new >= (1 << 24)) return FA_ERROR_ENCODE_PROCESS;  // SEEKTABLE block length is 24 bit
+    pl->whole = n_parts == 1;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t o = 0;
+    pl->off_parts = o; o += up((size_t)n_parts * sizeof(JoinPart));
+    pl->off_D = o; o += up((size_t)n_parts * (size_t)n_stream * 8);
+    pl->off_small = o; o += 256;
+    pl->total = o;
+    return FA_ERROR_NONE;
+}
+
+int64_t fa_join_workspace_bytes(int64_t n_parts, int64_t n_stream, const int64_t* stream_sizes, int channels, uint32_t level) {
+    JoinPlan pl;
+    return make_join_plan(channels, n_parts, n_stream, stream_sizes, level, &pl) ? -1 : (int64_t)pl.total;
+}
+// new size of stream s = 46 + sum_p (nbytes_p(s) - 46 + growth_p): the seek points only move
+int64_t fa_join_capacity_bytes(int64_t n_parts, const int64_t* n_old_bytes, int64_t n_stream, const int64_t* stream_sizes, int channels,
+                               uint32_t level) {
+    JoinPlan pl;
+    if (make_join_plan(channels, n_parts, n_stream, stream_sizes, level, &pl) || !n_old_bytes) return -1;
+    int64_t cap = n_stream * (46 + pl.growth_sum);
+    for (int64_t p = 0; p < n_parts; ++p) {
+        if (n_old_bytes[p] < 0 || n_old_bytes[p] > INT64_MAX - cap) return -1;
+        cap += n_old_bytes[p];
+    }
+    return cap;
+}
+
+int fa_join_device(int64_t n_parts, const unsigned char* const* d_old, const int64_t* n_old_bytes, const int64_t* const* d_old_starts,
+                   const int64_t* const* d_old_nbytes, const int64_t* stream_sizes, int64_t n_stream, int channels, uint32_t level,
+                   void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
+                   int64_t* d_nbytes, int64_t* h_total_bytes, void* stream) {
+    FA_API_LOCK;
+    if (!h_total_bytes) return FA_ERROR_ALLOC;
+    *h_total_bytes = 0;
+    JoinPlan pl;
+    int rc = make_join_plan(channels, n_parts, n_stream, stream_sizes, level, &pl);
+    if (rc) return rc;
+    if (n_stream == 0) return FA_ERROR_NONE;  // an empty store: nothing to launch
+    if (!d_old || !n_old_bytes || !d_old_starts || !d_old_nbytes || !d_starts || !d_nbytes) return FA_ERROR_DECODE_INIT;
+    for (int64_t p = 0; p < n_parts; ++p)
+        if (n_old_bytes[p] <= 0 || !d_old[p] || !d_old_starts[p] || !d_old_nbytes[p]) return FA_ERROR_DECODE_INIT;
+    if (!d_workspace || workspace_bytes < (int64_t)pl.total) return FA_ERROR_ALLOC;
+    if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
+    // (the copy reads its sources in aligned 16-byte blocks)
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 15) return FA_ERROR_ENCODE_INIT;
+    for (int64_t p = 0; p < n_parts; ++p)
+        if (reinterpret_cast<uintptr_t>(d_old[p]) & 15) return FA_ERROR_ENCODE_INIT;
+    const int64_t nchk = pl.whole ? 1 : pl.nf_new;
+    const int64_t nt = n_stream * nchk;
+    if (nt >= (1LL << 31) * 256) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* ws = reinterpret_cast<char*>(d_workspace);
+    std::vector<JoinPart> h_parts((size_t)n_parts);
+    for (int64_t p = 0; p < n_parts; ++p) {
+        JoinPart& q = h_parts[(size_t)p];
+        q.old = d_old[p]; q.old_bytes = n_old_bytes[p]; q.old_starts = d_old_starts[p]; q.old_nbytes = d_old_nbytes[p];
+        q.size = stream_sizes[p]; q.nf = pl.nf[(size_t)p]; q.base = pl.base[(size_t)p]; q.growth = pl.growth[(size_t)p];
+    }
+    JoinArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.part = reinterpret_cast<const JoinPart*>(ws + pl.off_parts);
+    a.D = reinterpret_cast<int64_t*>(ws + pl.off_D);
+    a.starts = d_starts; a.nbytes = d_nbytes; a.out = d_bytes;
+    a.err = reinterpret_cast<int*>(ws + pl.off_small);
+    a.P = n_parts; a.n_stream = n_stream; a.size_new = pl.size_new; a.nf_new = pl.nf_new; a.nchk = nchk;
+    a.B = (int32_t)pl.B; a.nch = channels; a.whole = pl.whole ? 1 : 0;
+    // 0. the layout of every stream of every part and every seek offset the copy follows; 1. sizes and starts (one wait:
+    // the error word and the total, which also keeps the host's descriptors alive until they are uploaded)
+    int64_t* d_total = reinterpret_cast<int64_t*>(ws + pl.off_small + 8);
+    FA_HIP_TRY(hipMemsetAsync(ws + pl.off_small, 0, 16, st));
+    FA_HIP_TRY(hipMemcpyAsync(ws + pl.off_parts, h_parts.data(), (size_t)n_parts * sizeof(JoinPart), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(join_check_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(join_size_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(starts_scan_kernel, dim3(1), dim3(1024), 0, st, d_nbytes, n_stream, d_starts, d_total);
+    struct { int32_t err, pad; int64_t total; } back = {0, 0, 0};
+    FA_HIP_TRY(hipMemcpyAsync(&back, a.err, sizeof back, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (back.err & kJoinBadLayout) return FA_ERROR_DECODE_INIT;
+    if (back.err) return FA_ERROR_DECODE_SEEK;
+    if (back.total <= 0 || back.total > capacity_bytes) return FA_ERROR_ALLOC;
+    // 2. the copy.  Workgroups per stream: ~64 KB of the result each (at most 1024, and a grid of fewer than 2^23 workgroups)
+    int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, back.total / n_stream / 65536));
+    while (parts > 1 && n_stream * parts >= (1LL << 23)) parts >>= 1;
+    if (n_stream * parts >= (1LL << 23)) return FA_ERROR_ALLOC;
+    a.parts = (int32_t)parts;
+    hipLaunchKernelGGL(join_kernel, dim3((unsigned)(n_stream * parts)), dim3(256), 0, st, a);
     FA_HIP_TRY(hipGetLastError());
     *h_total_bytes = back.total;
     return FA_ERROR_NONE;

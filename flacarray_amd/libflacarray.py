@@ -1975,3 +1975,166 @@ def window_flac_device(compressed, starts, nbytes, stream_size, first=0, last=No
                     hit = diff.any(dim=1)
                     _raise_on_mismatch(torch.where(hit, diff.int().argmax(dim=1) + (n - r), torch.full_like(hit, -1, dtype=torch.int64)))
     return out
+
+
+def _join_args(n_streams, stream_sizes, level):
+    """The argument checks of a join (ValueError, before anything touches the GPU): `n_streams` and `stream_sizes` hold
+    one value per part.  Returns (block size, the stream sizes as ints, j): j is None when every part but the last is a
+    whole number of blocks long (the aligned route takes all parts), else the index of the first part, other than the
+    last, behind which the running total is not a multiple of the block size."""
+    n_streams = [int(v) for v in n_streams]
+    sizes = [int(v) for v in stream_sizes]
+    if not sizes or len(n_streams) != len(sizes):
+        raise ValueError("a join needs at least one store (and one stream size per store)")
+    if level < 0 or level > 8:
+        raise ValueError("FLAC only supports compression levels 0-8")
+    if any(v <= 0 for v in sizes):
+        raise ValueError("You must specify the non-zero stream size of every part (there is no zero-sample stream to join)")
+    if any(v != n_streams[0] for v in n_streams):
+        raise ValueError(f"the parts of a join need one number of streams each, got {n_streams}")
+    if sum(sizes) >= 1 << 36:
+        raise ValueError("a FLAC stream holds fewer than 2^36 samples")
+    B = 1152 if level <= 2 else 4096
+    j, total = None, 0
+    for p, v in enumerate(sizes[:-1]):
+        total += v
+        if total % B:
+            j = p
+            break
+    return B, sizes, j
+
+
+def _join_aligned(L, stores, sizes, n_stream, nch, level, dev):
+    """One call of fa_join_device: (worst-case buffer, starts, nbytes, bytes used)."""
+    torch = _torch()
+    P = len(stores)
+    arr = ctypes.c_int64 * P
+    ptrs = ctypes.c_void_p * P
+    c_sizes = arr(*sizes)
+    c_bytes = arr(*[int(s[0].numel()) for s in stores])
+    ws_bytes = L.fa_join_workspace_bytes(P, n_stream, c_sizes, nch, level)
+    cap = L.fa_join_capacity_bytes(P, c_bytes, n_stream, c_sizes, nch, level)
+    if ws_bytes < 0 or cap < 0:
+        raise RuntimeError("Joining failed: invalid geometry")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    buf = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+    index = torch.empty(2 * n_stream, dtype=torch.int64, device=dev)
+    total = ctypes.c_int64(0)
+    errcode = L.fa_join_device(P, ptrs(*[s[0].data_ptr() for s in stores]), c_bytes, ptrs(*[s[1].data_ptr() for s in stores]),
+                               ptrs(*[s[2].data_ptr() for s in stores]), c_sizes, n_stream, nch, level, _dp(ws), ws.numel(), _dp(buf), cap,
+                               _dp(index[:n_stream]), _dp(index[n_stream:]), ctypes.byref(total), _stream_ptr())
+    if errcode == 8192:  # FA_ERROR_DECODE_INIT
+        raise ValueError(f"Joining needs streams written by this library (a SEEKTABLE with one point per frame; reindex() adopts other "
+                         f"stores) with the block size of level {level}, {nch} channel(s) and the stream sizes {sizes}")
+    if errcode == 1 << 18:  # FA_ERROR_DECODE_SEEK
+        raise RuntimeError("Joining failed: a seek table's offsets are not ordered inside the stream body, or a frame is shorter than "
+                           "its header plus the CRC-16")
+    if errcode != 0:
+        raise RuntimeError(f"Joining failed, return code = {errcode}")
+    return buf, index[:n_stream], index[n_stream:], total.value
+
+
+def join_flac_device(stores, level=5, is_int64=False, verify=False, compact=False, max_temp_bytes=None):
+    """Put device-resident stores behind one another along the sample axis as a NEW store: `stores` is a sequence of
+    (compressed, starts, nbytes, stream_size) on one GPU, all of one number of streams; returns the new (compressed,
+    starts, nbytes), all on the device (starts / nbytes have the shape of the first part's), the arguments left as they
+    are.  A single part is copied verbatim, its STREAMINFO MD5 included; every other result has a zero one.
+
+    Every part must have this library's layout (one SEEKTABLE point per frame; reindex_flac_device adopts others) and
+    `level` the level ALL parts were written at (its block size B is checked against the streams' STREAMINFO).  For
+    streams of integers the result is then byte for byte encode_flac_device(cat(x_i, dim=-1), level) with x_i the decoded
+    parts (for float stores written with one set of offsets and gains: of the quantised integers), for any number of
+    parts of any lengths.
+
+    Every part but the last a whole number of blocks long (fa_join_device, include/flacarray_hip.h, K15): no sample is
+    decoded and nothing is encoded.  The frames of part p are copied with their numbers raised by the frames in front of
+    them (number field, CRC-8, CRC-16 by its linear identity), the seek table is rebuilt in closed form from the parts'
+    tables, and the first part, whose numbers and offsets do not change, moves as two plain copies.
+
+    Otherwise, with j the first part (other than the last) behind which the running total is not a multiple of B, every
+    frame behind that point changes, and this route COSTS A DECODE PLUS AN ENCODE of everything behind the first
+    unaligned boundary: parts 0 .. j are joined as above (part j is the last of that call, so it may be short), and the
+    remaining parts are decoded and appended with append_flac_device, whose any-split contract makes the result the
+    one-shot encode.  That is done in row chunks of at most `max_temp_bytes` of decoded samples (default 256 MiB, at least
+    one row): each chunk selects its rows of the joined prefix through window_flac_device(streams=...) (pure selection)
+    and the pieces are put back to back.  At 4096 x 2^20 and the default chunk size IT IS SLOWER THAN DECODING THOSE PARTS
+    AND APPENDING THEM IN ONE GO, 71 ms against 28 ms, for 24.6 GB of extra memory against 39.7 GB (profiles/join.md).
+
+    `compressed` is a view of a buffer sized for the worst case (the parts' bytes plus the grown headers), which it keeps
+    alive; `compact=True` returns an exact-size copy instead.  `verify=True`: frame_status_device over the RESULT must be
+    all zero (every frame carries its new number, its block size, a clean CRC-8 and CRC-16), else RuntimeError naming the
+    first (stream, frame, status); on the unaligned route the appended span is also verified as append_flac_device(verify=
+    True) does.
+
+    ValueError: no store, a level outside 0-8, parts of different stream counts, a stream size <= 0, or streams that are
+    not this library's for the call's block size, channel count (is_int64: two) and stream sizes.  RuntimeError: a seek
+    table whose offsets are not ordered inside the stream body or a frame shorter than its header plus CRC-16 (refused by
+    the check kernel's error word before anything is read through such an offset).  At most 65536 parts per call."""
+    torch = _torch()
+    stores = [tuple(s) for s in stores]
+    for s in stores:
+        if len(s) != 4:
+            raise ValueError("every store of a join is (compressed, starts, nbytes, stream_size)")
+        if s[0].dtype != torch.uint8:
+            raise ValueError("Compressed data should be of type uint8")
+        if s[1].dtype != torch.int64 or s[2].dtype != torch.int64 or s[1].shape != s[2].shape:
+            raise ValueError("starts and nbytes should be int64 tensors of one shape")
+    B, sizes, j = _join_args([int(np.prod(s[1].shape)) for s in stores], [s[3] for s in stores], level)
+    if len(stores) > 65536:
+        raise ValueError("a join takes at most 65536 parts per call (join the parts in groups)")
+    dev = stores[0][0].device
+    if not all(t.is_cuda and t.device == dev for s in stores for t in s[:3]):
+        raise RuntimeError("join_flac_device needs every compressed, starts and nbytes on the same GPU")
+    out_shape = tuple(stores[0][1].shape)
+    n_stream = int(np.prod(out_shape))
+    if n_stream == 0:
+        return stores[0][0].new_empty(0), stores[0][1].new_empty(out_shape), stores[0][2].new_empty(out_shape)
+    nch = 2 if is_int64 else 1
+    L = _lib.lib()
+    with _on_device(dev):
+        flat = []
+        for comp, st, nb, _ in stores:
+            comp = comp.contiguous()
+            if comp.data_ptr() & 15:  # (the copy reads its sources in aligned 16-byte blocks)
+                comp = comp.clone()
+            flat.append((comp, st.reshape(-1).contiguous(), nb.reshape(-1).contiguous()))
+        n_pre = len(flat) if j is None else j + 1
+        buf, starts2, nbytes2, total = _join_aligned(L, flat[:n_pre], sizes[:n_pre], n_stream, nch, level, dev)
+        blob = buf[:total]
+        if j is not None:
+            # unaligned: the rest is decoded and appended, a chunk of rows at a time
+            size_pre, n_rest = sum(sizes[:n_pre]), sum(sizes[n_pre:])
+            cap = (256 << 20) if max_temp_bytes is None else int(max_temp_bytes)
+            per = max(1, cap // (n_rest * 4 * nch))
+            blobs, counts = [], []
+            for r0 in range(0, n_stream, per):
+                r1 = min(r0 + per, n_stream)
+                if r1 - r0 == n_stream:
+                    sub = (blob, starts2, nbytes2)
+                else:
+                    sub = window_flac_device(blob, starts2, nbytes2, size_pre, streams=np.arange(r0, r1), level=level, is_int64=is_int64)
+                xs = [decode_flac_device(c, st[r0:r1], nb[r0:r1], n, is_int64=is_int64).reshape(r1 - r0, n)
+                      for (c, st, nb), n in zip(flat[n_pre:], sizes[n_pre:])]
+                x = xs[0] if len(xs) == 1 else torch.cat(xs, dim=1)
+                del xs
+                # (compact: a piece must not keep its worst-case buffer alive while the others are made)
+                b, _, nbs = append_flac_device(sub[0], sub[1], sub[2], size_pre, x.contiguous(), level=level, verify=bool(verify), compact=True)
+                blobs.append(b)
+                counts.append(nbs.reshape(-1))
+                del x, sub
+            del buf
+            nbytes2 = torch.cat(counts)
+            starts2 = torch.cumsum(nbytes2, 0) - nbytes2
+            blob = torch.cat(blobs) if len(blobs) > 1 else blobs[0]  # (exact-size either way)
+        elif compact:
+            blob = blob.clone()
+            del buf
+        out = (blob, starts2.reshape(out_shape), nbytes2.reshape(out_shape))
+        if verify:
+            status = frame_status_device(out[0], starts2, nbytes2, sum(sizes), is_int64=is_int64, block_size=B)
+            bad = torch.nonzero(status.reshape(n_stream, -1))
+            if bad.numel():
+                s_bad, f_bad = (int(v) for v in bad[0])
+                raise RuntimeError(f"Joining failed: {bad.shape[0]} frame(s) of the result do not check (first: stream {s_bad}, frame {f_bad}, "
+                                   f"status {int(status.reshape(n_stream, -1)[s_bad, f_bad])})")
+    return out

@@ -519,6 +519,42 @@ int fa_window_device(const unsigned char* d_old, int64_t n_old_bytes, const int6
                      void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
                      int64_t* d_nbytes, int64_t* h_total_bytes, void* stream);
 
+/* Join: put the streams of n_parts stores of n_stream streams each behind one another along the sample axis as a NEW
+ * store, without decoding a sample or re-encoding a frame (join_kernels.hpp, K15; the inverse of the window).  Part p
+ * holds stream_sizes[p] samples per stream; every part but the last must be a whole number of blocks B of `level` long
+ * (FA_ERROR_DECODE_SAMPLE_RANGE otherwise: every frame boundary behind an unaligned part moves, and the decode and encode
+ * that takes is the caller's to do; the same code for a total of 2^36 samples or more).  With base_p the frames in front
+ * of part p, frame k of part p is copied as frame base_p + k (the UTF-8 number field, which may get longer, the header
+ * CRC-8, and the CRC-16 through its linear identity: no pass over a payload), the seek table is rebuilt in closed form
+ * from the parts' tables, and the stream header is written for the total samples with a zero MD5.  For integer stores
+ * the result is byte for byte the encode of the concatenated decoded parts at `level`, provided that is the level every
+ * part was written at.  Two shortcuts: part 0 changes neither numbers nor offsets, its seek points and frames are copied
+ * as they are; n_parts == 1 copies every stream verbatim, its STREAMINFO MD5 included.
+ * d_old, n_old_bytes, d_old_starts, d_old_nbytes and stream_sizes are HOST arrays of length n_parts (of device pointers,
+ * byte counts and sizes); the part descriptors travel to the device in the workspace, so n_parts is bounded by the
+ * implementation only: at most 65536 (FA_ERROR_ENCODE_PROCESS, as for more than 932 067 frames per stream, what the
+ * SEEKTABLE's 24-bit length holds).  n_parts <= 0 gives FA_ERROR_ZERO_NSTREAM, a stream size <= 0 FA_ERROR_ZERO_STREAMSIZE;
+ * n_stream == 0 returns FA_ERROR_NONE with a total of 0 and launches nothing.  channels: 1 for int32 / float32 arrays,
+ * 2 for int64 / float64 (no sample format enters the copy).  Every stream of every part must be one this library wrote
+ * for the call's block size, channel count and that part's stream size, with one seek point per frame
+ * (FA_ERROR_DECODE_INIT otherwise; fa_reindex_device adopts other stores), and every seek offset of every part must be
+ * ordered inside the stream's body and leave each frame its own header plus the CRC-16, at least 13 bytes
+ * (FA_ERROR_DECODE_SEEK otherwise).  Both are checked by one kernel before anything is copied, and on every error nothing
+ * is written to d_bytes.  Every d_old[p] and d_workspace must be 16-byte aligned (FA_ERROR_ENCODE_INIT); the parts are
+ * unchanged, may be one and the same store, and d_bytes must not overlap them.  fa_join_workspace_bytes() is the
+ * workspace the call needs; fa_join_capacity_bytes() a capacity that always suffices: the parts' bytes plus
+ * n_stream * (46 + the growth of the number fields), since the seek points only move; a smaller buffer gives
+ * FA_ERROR_ALLOC if the result does not fit.  Both return -1 for arguments the call refuses.  The new streams lie back to
+ * back from 0, d_starts / d_nbytes [n_stream] are their index, *h_total_bytes the bytes used; no byte of d_bytes from
+ * there on is written.  All work is issued on `stream`; the copy is not waited for, and reads the workspace. */
+int64_t fa_join_workspace_bytes(int64_t n_parts, int64_t n_stream, const int64_t* stream_sizes, int channels, uint32_t level);
+int64_t fa_join_capacity_bytes(int64_t n_parts, const int64_t* n_old_bytes, int64_t n_stream, const int64_t* stream_sizes, int channels,
+                               uint32_t level);
+int fa_join_device(int64_t n_parts, const unsigned char* const* d_old, const int64_t* n_old_bytes, const int64_t* const* d_old_starts,
+                   const int64_t* const* d_old_nbytes, const int64_t* stream_sizes, int64_t n_stream, int channels, uint32_t level,
+                   void* d_workspace, int64_t workspace_bytes, unsigned char* d_bytes, int64_t capacity_bytes, int64_t* d_starts,
+                   int64_t* d_nbytes, int64_t* h_total_bytes, void* stream);
+
 /* Batched random access: slice i is samples [first[i], first[i]+count[i]) of stream
  * slice_stream[i]; its samples are written at element offset out_offset[i] of the output.
  * The four slice arrays are HOST arrays of length n_slices.  The reference needs one
@@ -585,7 +621,7 @@ const char* fa_version(void);
  * do not / process default, see fa_set_decode_verify; revision 3 added the std entry points, revision 4 the compare entry
  * points and fa_set_encode_verify); a binding built against
  * another revision must refuse the library instead of calling it with a shifted argument list --
- * flacarray_amd/_lib.py does.  Entry points that are only added (the append, MD5, overwrite, damage-map and reindex groups) leave it as it is. */
+ * flacarray_amd/_lib.py does.  Entry points that are only added (the append, MD5, overwrite, damage-map, reindex, window and join groups) leave it as it is. */
 #define FA_ABI_VERSION 4  /* (revision 4: fa_compare_i32_device / fa_compare_i64_device / fa_set_encode_verify) */
 int fa_abi_version(void);
 
