@@ -2882,6 +2882,7 @@ int fa_join_device(int64_t n_parts, const unsigned char* const* d_old, const int
 
 int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t stream_size, const float* d_quanta,
                                int32_t* d_output, float* d_offsets, float* d_gains, void* stream) {
+    if (n_stream > INT32_MAX) return FA_ERROR_CONVERT_TYPE;  // one workgroup per stream: the grid's bound (before anything is touched)
     FA_API_LOCK;
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
@@ -2904,10 +2905,11 @@ int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t s
 
 int fa_int32_to_float32_device(const int32_t* d_input, int64_t n_stream, int64_t stream_size, const float* d_offsets,
                                const float* d_gains, float* d_output, void* stream) {
-    FA_API_LOCK;
     if (n_stream <= 0 || stream_size <= 0) return FA_ERROR_NONE;
+    const int64_t cps = (stream_size - 1) / kDequantChunk + 1;
+    if (n_stream > INT32_MAX / cps) return FA_ERROR_CONVERT_TYPE;  // one workgroup per chunk: the grid's bound (before anything is touched)
+    FA_API_LOCK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t cps = (stream_size + kDequantChunk - 1) / kDequantChunk;
     hipLaunchKernelGGL(int32_to_float32_kernel, dim3((unsigned)(n_stream * cps)), dim3(256), 0, st, d_input, stream_size, cps,
                        d_offsets, d_gains, d_output);
     FA_HIP_TRY(hipGetLastError());
@@ -2916,6 +2918,7 @@ int fa_int32_to_float32_device(const int32_t* d_input, int64_t n_stream, int64_t
 
 int fa_float64_to_int64_device(const double* d_input, int64_t n_stream, int64_t stream_size, const double* d_quanta,
                                int64_t* d_output, double* d_offsets, double* d_gains, void* stream) {
+    if (n_stream > INT32_MAX) return FA_ERROR_CONVERT_TYPE;  // one workgroup per stream: the grid's bound (before anything is touched)
     FA_API_LOCK;
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_ZERO_STREAMSIZE;
@@ -2936,10 +2939,11 @@ int fa_float64_to_int64_device(const double* d_input, int64_t n_stream, int64_t 
 
 int fa_int64_to_float64_device(const int64_t* d_input, int64_t n_stream, int64_t stream_size, const double* d_offsets,
                                const double* d_gains, double* d_output, void* stream) {
-    FA_API_LOCK;
     if (n_stream <= 0 || stream_size <= 0) return FA_ERROR_NONE;
+    const int64_t cps = (stream_size - 1) / kDequantChunk + 1;
+    if (n_stream > INT32_MAX / cps) return FA_ERROR_CONVERT_TYPE;  // one workgroup per chunk: the grid's bound (before anything is touched)
+    FA_API_LOCK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t cps = (stream_size + kDequantChunk - 1) / kDequantChunk;
     hipLaunchKernelGGL(int64_to_float64_kernel, dim3((unsigned)(n_stream * cps)), dim3(256), 0, st, d_input, stream_size, cps,
                        d_offsets, d_gains, d_output);
     FA_HIP_TRY(hipGetLastError());

@@ -572,7 +572,9 @@ int fa_decode_slices_i64_device(const unsigned char* d_bytes, int64_t n_bytes, c
                                 const double* d_offsets, const double* d_gains, void* stream, int verify);
 
 /* float32 -> int32 quantisation on device; d_quanta may be NULL.  Returns FA_ERROR_NAN_INPUT
- * if any input is NaN (outputs are then unspecified). */
+ * if any input is NaN (outputs are then unspecified).  The four conversions of this group launch one workgroup per
+ * stream (to integers) or per 16384-sample chunk of a stream (to floats): more than 2^31 - 1 of them are refused with
+ * FA_ERROR_CONVERT_TYPE before anything is launched or touched (convert the streams in groups). */
 int fa_float32_to_int32_device(const float* d_input, int64_t n_stream, int64_t stream_size, const float* d_quanta,
                                int32_t* d_output, float* d_offsets, float* d_gains, void* stream);
 
