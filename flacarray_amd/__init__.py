@@ -6,7 +6,7 @@ Drop-in names of the reference (hpc4cmb/flacarray): `array_compress`, `array_dec
 BASELINE.json.  All compute runs in hand-written HIP kernels (libflacarray_hip.so); there is
 no CPU fallback.
 """
-from .array import FlacArray, StreamStats
+from .array import FlacArray, StreamHistogram, StreamStats
 from .compress import array_compress
 from .decompress import array_decompress, array_decompress_slice
 from .libflacarray import (
@@ -29,6 +29,7 @@ from .libflacarray import (
     md5_device,
     overwrite_flac_device,
     reduce_flac_device,
+    histogram_flac_device,
     reindex_flac_device,
     set_decode_verify,
     set_encode_md5,
@@ -47,6 +48,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "FlacArray",
+    "StreamHistogram",
     "StreamStats",
     "DeviceDecodeIndex",
     "append_flac_device",
@@ -75,6 +77,7 @@ __all__ = [
     "FRAME_CRC16",
     "compare_flac_device",
     "reduce_flac_device",
+    "histogram_flac_device",
     "md5_device",
     "check_md5_device",
     "sign_streams_device",

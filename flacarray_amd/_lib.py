@@ -74,6 +74,9 @@ SYMBOLS = [
     "fa_reduce_i32_device",
     "fa_reduce_i64_device",
     "fa_reduce_indexed",
+    "fa_histogram_i32_device",
+    "fa_histogram_i64_device",
+    "fa_histogram_indexed",
     "fa_frame_status_device",
     "fa_fill_ranges_device",
     "fa_decode_salvage_i32_device",
@@ -245,6 +248,12 @@ def lib():
     L.fa_reduce_i64_device.restype = cint
     L.fa_reduce_indexed.argtypes = [vp, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, cint]
     L.fa_reduce_indexed.restype = cint
+    L.fa_histogram_i32_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, cint]
+    L.fa_histogram_i32_device.restype = cint
+    L.fa_histogram_i64_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, cint]
+    L.fa_histogram_i64_device.restype = cint
+    L.fa_histogram_indexed.argtypes = [vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, cint]
+    L.fa_histogram_indexed.restype = cint
     L.fa_frame_status_device.argtypes = [vp, i64, vp, vp, i64, i64, cint, i64, vp, vp]
     L.fa_frame_status_device.restype = cint
     L.fa_fill_ranges_device.argtypes = [vp, cint, i64, vp, vp, vp, vp]

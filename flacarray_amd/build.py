@@ -18,6 +18,7 @@ DEPS = [
     os.path.join(_HERE, "csrc", "std_kernels.hpp"),
     os.path.join(_HERE, "csrc", "splice_kernels.hpp"),
     os.path.join(_HERE, "csrc", "reduce_kernels.hpp"),
+    os.path.join(_HERE, "csrc", "histogram_kernels.hpp"),
     os.path.join(_HERE, "csrc", "scrub_kernels.hpp"),
     os.path.join(_HERE, "csrc", "reindex_kernels.hpp"),
     os.path.join(_HERE, "csrc", "window_kernels.hpp"),

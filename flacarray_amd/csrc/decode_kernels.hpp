@@ -503,13 +503,13 @@ struct DecodeArgs {
     // outputs.  (The unions: the reducing sink, which has no use for the store's, the restore's, the two-channel image's or
     // the compare sink's arguments, keeps its own in their places -- the layout, and with it the code of every other
     // instantiation, is what it was without that sink.)
-    union { int32_t* out_i32; long long* red_min; };
-    union { float* out_f32; long long* red_max; };                 // when non-null: dequantised output instead of out_i32
-    union { const float* offsets; long long* red_sum; };           // per stream
-    union { const float* gains; unsigned long long* red_sq_hi; };
+    union { int32_t* out_i32; long long* red_min; unsigned long long* hist_counts; };
+    union { float* out_f32; long long* red_max; unsigned long long* hist_below; };                 // when non-null: dequantised output instead of out_i32
+    union { const float* offsets; long long* red_sum; unsigned long long* hist_above; };           // per stream
+    union { const float* gains; unsigned long long* red_sq_hi; const long long* hist_lo; };
     int* err;
     // two-channel arrays (NCH == 2): out_i32 is then the task-local planar image
-    union { uint32_t* hibits; unsigned long long* red_sq_lo; };   // [n_tasks][2][hib_words] bit 32 of every sample
+    union { uint32_t* hibits; unsigned long long* red_sq_lo; const int32_t* hist_shift; };   // [n_tasks][2][hib_words] bit 32 of every sample
     int32_t* assign;    // [n_tasks] channel assignment once both subframes are decoded, else -1
     int32_t hib_words;  // ceil(B / 32)
     int32_t verbatim_done;  // NCH == 2: VERBATIM first subframes (no wasted bits) were decoded by verbatim_channel0_kernel
@@ -522,6 +522,10 @@ struct DecodeArgs {
     // radix-2^32 limbs of its sum of squares land in red_*[row * red_nbins + bin].  Grid mode: row = stream; list mode:
     // task_out_off carries row * red_nbins.  The arrays hold the identities (INT64_MAX, INT64_MIN, 0) before the launch;
     // red_sq_hi / red_sq_lo may be null together.
+    // histogram sink (decode_frames_kernel<..., HIST = true>; one channel): rows as for the reducing sink, red_nbins value
+    // bins per row (1..2048).  A sample x of row r below hist_lo[r] counts in hist_below[r]; otherwise its bin is
+    // ((uint64)x - (uint64)hist_lo[r]) >> hist_shift[r], counted in hist_counts[r * red_nbins + bin] or, from red_nbins
+    // on, in hist_above[r].  The three arrays hold zeros before the launch; red_width is not used.
     union { const void* cmp; int64_t red_width; };
     union { unsigned long long* first_mismatch; int64_t red_nbins; };
 };
@@ -590,6 +594,7 @@ constexpr int kRingW = 2 * kChunkW;                   // ring words without the 
 constexpr int kDecRingWords = kRingW + 2;             // + 2 mirror words, per lane
 constexpr int kTopup = kChunkBytes / 8;               // samples between top-ups (<= 4 bytes per fast sample)
 constexpr int kLaneStride = 64;  // word j of lane l lives at j*64 + l: the bank depends on the lane only
+constexpr int kHistMaxBins = 2048;  // K7H: bins per row at most -- its LDS histogram is then as large as the 32-sample tile image
 
 constexpr int kFlagNeed16 = 1, kFlagNeed32 = 2;
 __device__ __forceinline__ int4 shl4(const int4& v, int n) {
@@ -790,7 +795,13 @@ __device__ __noinline__ BitsRet slow_sample(const uint8_t* cbase, const uint8_t*
 // writes them out at every bin boundary it crosses and at the end of its range -- with plain 8-byte stores when the bin
 // lies wholly inside the lane's range (it then has no other contributor), with 64-bit atomics onto the pre-set
 // identities when two frames share it.  No tile image, no cooperative store, no row table.
-template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false>
+// HIST (one channel, integers): the histogram sink, K7H.  Where the reducing sink folds a sample, this one counts it in a
+// value bin of its row (DecodeArgs: hist_*).  A wave whose tasks all belong to one row counts in a histogram of
+// red_nbins uint32 words in LDS, behind the ring image where the storing instantiation keeps its tile, and adds the
+// non-zero words to hist_counts when its frames are done; a wave that holds several rows (short streams, the seam
+// between two streams) adds every sample straight to hist_counts.  Both use 64-bit relaxed atomics of agent scope:
+// integer adds commute, so the counts do not depend on the order of arrival.
+template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false, bool HIST = false>
 #ifndef FA_K7_WAVES_ATTR
 #define FA_K7_WAVES_ATTR
 #endif
@@ -802,12 +813,17 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     constexpr int kTileSwz = 32 / kTileG;
     static_assert(NCH == 1 || (kTileW == 32 && !F32), "two-channel variant: 32-sample tiles, integer output");
     static_assert(!RED || (NCH == 1 && !F32 && !CMP), "reducing sink: one channel, integer domain");
+    static_assert(!HIST || (NCH == 1 && !F32 && !CMP && !RED), "histogram sink: one channel, integer domain");
+    constexpr bool FOLD = RED || HIST;  // no tile image, no cooperative store: every sample goes to the sink from its register
     constexpr bool SINK = CMP && NCH == 1;  // the tile store compares instead of writing
     // one LDS object, so that the ring image starts at LDS address 0 (ring_words builds its addresses with an OR)
-    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + (RED ? 0 : kTileW * kLaneStride) + (F32 ? 128 : 0)];
+    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + (HIST ? kHistMaxBins : RED ? 0 : kTileW * kLaneStride) + (F32 ? 128 : 0)];
     uint32_t* const rings = lds_k7;
     int32_t* const tile = reinterpret_cast<int32_t*>(lds_k7 + kDecRingWords * kLaneStride);  // sample t of lane l at t*64 + (l ^ 8*(t>>2))
     float2* const row_fg = reinterpret_cast<float2*>(lds_k7 + kDecRingWords * kLaneStride + kTileW * kLaneStride);
+    // K7H: the wave's histogram, one uint32 word per bin.  A wave holds 64 frames of at most 65535 samples each (a FLAC
+    // frame's limit; the driver refuses block sizes beyond 65536), so a word counts at most 2^22 samples: uint32 is enough.
+    uint32_t* const hist = lds_k7 + kDecRingWords * kLaneStride;
     const int lane = threadIdx.x;
     const int64_t task = (int64_t)blockIdx.x * 64 + lane;
     const bool has_task = task < a.n_tasks;
@@ -828,11 +844,31 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         } else {
             s = task / a.nfr; f = a.f0 + (task - s * a.nfr);
             sl_first = a.first; sl_last = a.first + a.n_decode;
-            if constexpr (RED) out_off = s * a.red_nbins;
+            if constexpr (FOLD) out_off = s * a.red_nbins;
             else out_off = s * a.n_decode;
         }
     }
     const int64_t fstart = f * (int64_t)a.B;
+    // K7H: the lane's row and its bin parameters; `hist_one`: every task of this wave belongs to row hist_row0 (lane 0
+    // always holds a task), so the wave counts in LDS
+    int64_t hist_row = -1, hist_row0 = 0;
+    long long hist_l = 0;
+    uint32_t hist_sh = 0, hist_nb = 0, hist_bel = 0, hist_abv = 0;  // (a lane counts at most the samples of its frame)
+    bool hist_one = false;
+    if constexpr (HIST) {
+        hist_nb = (uint32_t)a.red_nbins;
+        if (has_task) {
+            hist_row = a.task_stream ? out_off / a.red_nbins : s;
+            hist_l = a.hist_lo[hist_row];
+            hist_sh = (uint32_t)a.hist_shift[hist_row] & 63u;
+        }
+        hist_row0 = __shfl(hist_row, 0, 64);
+        hist_one = __all(!has_task || hist_row == hist_row0);
+        if (hist_one) {
+            for (uint32_t b = (uint32_t)lane; b < hist_nb; b += 64) hist[b] = 0u;
+        }
+        __syncthreads();  // (the workgroup is this wave)
+    }
     // a frame the decoder rejects: the error word, or (compare sink) a mismatch at the frame's first sample
     auto reject = [&]() __attribute__((always_inline)) {
         if constexpr (CMP) atomicMin(a.first_mismatch + s, (unsigned long long)fstart);
@@ -993,7 +1029,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             // ---- warm-up samples, predictor description, residual header (serial per lane) ----
             for (int i = 0; i < order; ++i) {
                 const double x = get_wide(bps);
-                if constexpr (!RED) {  // (the reducing sink takes the warm-up samples from the history, in the sample loop)
+                if constexpr (!FOLD) {  // (the reducing sink takes the warm-up samples from the history, in the sample loop)
                     if (i < kTileW) {
                         tile[i * kLaneStride + (lane ^ ((i >> 2) * kTileSwz))] = wrap32(x);  // (wasted bits are restored in flush_tile)
                         if constexpr (NCH == 2) hbw |= (x < 0.0) ? (1u << i) : 0u;
@@ -1114,14 +1150,14 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     __builtin_amdgcn_wave_barrier();
     int64_t row0;  // output element index of frame sample 0
     if constexpr (NCH == 2) row0 = (task * 2 + chn) * (int64_t)a.B;
-    else if constexpr (RED) row0 = 0;  // (no rows: out_off is the lane's first bin slot)
+    else if constexpr (FOLD) row0 = 0;  // (no rows: out_off is the lane's first bin slot)
     else row0 = out_off + (fstart - sl_first);
     // The store pass `it` of a tile has this lane write a piece of row it * (64 / kTileG) + lane / kTileG: that
     // row's output offset is fetched from its owner lane once per frame and kept in registers (no LDS table:
     // the LDS saved is what lets more waves share a CU); the valid range is fetched in the rare clipped path.
     int64_t rout[kTileG];
 #pragma unroll
-    for (int it = 0; it < (RED ? 0 : kTileG); ++it) {
+    for (int it = 0; it < (FOLD ? 0 : kTileG); ++it) {
         const int r = it * (64 / kTileG) + (lane / kTileG);
         const uint32_t rl = (uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)(uint32_t)(uint64_t)row0);
         const uint32_t rh = (uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)(uint32_t)((uint64_t)row0 >> 32));
@@ -1233,6 +1269,21 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         }
         if (__builtin_expect(__any(i + 1 == red_end), 0)) {
             if (i + 1 == red_end) red_emit();
+        }
+    };
+
+    // histogram sink: sample i of the lane's frame (wasted bits not yet restored) into the bin of its value
+    auto hist_take = [&](int i, int32_t x0) __attribute__((always_inline)) {
+        if ((uint32_t)(i - lo) < (uint32_t)(hi - lo)) {
+            const long long x = (long long)(int32_t)((uint32_t)x0 << wasted);
+            if (x < hist_l) {
+                hist_bel++;
+            } else {
+                const unsigned long long b = ((unsigned long long)x - (unsigned long long)hist_l) >> hist_sh;  // exact: x >= lo
+                if (b >= (unsigned long long)hist_nb) hist_abv++;
+                else if (hist_one) (void)atomicAdd(hist + (uint32_t)b, 1u);
+                else (void)__hip_atomic_fetch_add(a.hist_counts + out_off + (int64_t)b, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     };
 
@@ -1383,6 +1434,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             h[u % MO] = xd;
             if constexpr (RED) {
                 red_take(i, wrap32(xd));
+            } else if constexpr (HIST) {
+                hist_take(i, wrap32(xd));
             } else {
 #if (FA_K7_X & 4)
             if (u == 0)
@@ -1393,6 +1446,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             if constexpr (RED) {
                 // every warm-up sample (i < order <= MO): its value sits in the history, slot i % MO = u % MO
                 if (i < bs) red_take(i, wrap32(h[u % MO]));
+            } else if constexpr (HIST) {
+                if (i < bs) hist_take(i, wrap32(h[u % MO]));  // (as above)
             } else {
             // warm-up sample 16..31 (orders above 16): its value sits in the history
             if (i < bs && i >= kTileW) tile[u * kLaneStride + (lane ^ ((u >> 2) * kTileSwz))] = wrap32(h[u % MO]);
@@ -1431,7 +1486,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
 
     // cooperative store of the tile: (64 / kTileG) rows x kTileW samples per pass, 16 bytes per lane
     auto flush_tile = [&](int tbase) __attribute__((always_inline)) {
-        if constexpr (RED) return;  // (no tile)
+        if constexpr (FOLD) return;  // (no tile)
         __builtin_amdgcn_wave_barrier();
         if constexpr (NCH == 2) {
             // bit 32 of this lane's 32 samples (tiles are 32 samples wide)
@@ -1660,6 +1715,24 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         }
     }
     }  // channel loop
+    if constexpr (HIST) {
+        // the wave's frames are done: its LDS histogram and the lanes' outlier counts go to the row's arrays
+        __syncthreads();
+        if (hist_one) {
+            for (uint32_t b = (uint32_t)lane; b < hist_nb; b += 64) {
+                const uint32_t c = hist[b];
+                if (c) (void)__hip_atomic_fetch_add(a.hist_counts + hist_row0 * a.red_nbins + b, (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                hist_bel += (uint32_t)__shfl_xor((int)hist_bel, off, 64);
+                hist_abv += (uint32_t)__shfl_xor((int)hist_abv, off, 64);
+            }
+            if (lane != 0) { hist_bel = 0; hist_abv = 0; }
+        }
+        if (hist_bel) (void)__hip_atomic_fetch_add(a.hist_below + hist_row, (unsigned long long)hist_bel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (hist_abv) (void)__hip_atomic_fetch_add(a.hist_above + hist_row, (unsigned long long)hist_abv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if constexpr (NCH == 2) {
         if (has_task && task_live) a.assign[task] = ch_assign;  // both subframes decoded
     }

@@ -40,6 +40,7 @@
 #include "splice_kernels.hpp"
 #include "md5_kernels.hpp"
 #include "reduce_kernels.hpp"
+#include "histogram_kernels.hpp"
 #include "scrub_kernels.hpp"
 #include "reindex_kernels.hpp"
 #include "window_kernels.hpp"
@@ -563,6 +564,7 @@ struct ReduceSink {
     int64_t width, nbins, n_sel;
     const int64_t* sel;
     ReduceOut out;
+    const HistOut* hist = nullptr;  // the histogram sink K7H in the reducing sink's place: nbins value bins per row, `width` and `out` unused
 };
 
 // device memory for a task table: the index's own (grown on demand) or the cached scratch
@@ -769,9 +771,15 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     if (a.B > kMaxBlock * 16) return FA_ERROR_DECODE_INIT;
     if (red) {
         if (n_slices >= 0) return FA_ERROR_CONVERT_TYPE;
+        if (red->hist) {
+            a.hist_counts = red->hist->counts; a.hist_below = red->hist->below; a.hist_above = red->hist->above;
+            a.hist_lo = red->hist->lo; a.hist_shift = red->hist->shift;
+            a.red_width = 0; a.red_nbins = red->nbins;
+        } else {
         a.red_min = red->out.mn; a.red_max = red->out.mx; a.red_sum = red->out.sum;
         a.red_sq_hi = red->out.sq_hi; a.red_sq_lo = red->out.sq_lo;
         a.red_width = red->width; a.red_nbins = red->nbins;
+        }
         if (red->sel) a.n_tasks = red->n_sel * a.nfr;  // list mode; the table is built on the device, below
         if (a.n_tasks <= 0 || a.n_tasks > (int64_t)64 * 0x7fffffff) return FA_ERROR_DECODE_SAMPLE_RANGE;
     }
@@ -941,7 +949,8 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     const bool verifying_k7 = (verify < 0 ? g_verify.load() : verify != 0);
     const bool beside = verifying_k7 && a.n_tasks >= 16384 && std::getenv("FLACARRAY_HIP_VERIFY_AFTER") == nullptr &&
                         run_verify_beside_begin(st);
-    if (red) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    else if (red) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     else if (cmp) {
         if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -954,7 +963,8 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
     if (h_err[1] & kFlagNeed16) {
-        if (red) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (red) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else if (cmp) {
             if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
             else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -962,7 +972,8 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     }
     if (h_err[1] & kFlagNeed32) {
-        if (red) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (red) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else if (cmp) {
             if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
             else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -2241,11 +2252,10 @@ static int reduce_peek_blocksize(const unsigned char* d_bytes, int64_t n_bytes, 
     return FA_ERROR_NONE;
 }
 
-static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
-                         int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel,
-                         const int64_t* d_sel, int64_t max_temp_bytes, int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi,
-                         uint64_t* d_sq_lo, void* stream, int verify) {
-    FA_API_LOCK;
+// What the reducing calls (fa_reduce_*, fa_histogram_*) share: the store named by an index or by its three arrays, the
+// sample range (both ends negative: everything)
+static int reduce_store_args(int nch, DecodeIndex* ix, const unsigned char*& d_bytes, int64_t& n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                             int64_t& n_stream, int64_t& stream_size, int64_t& first, int64_t& last) {
     if (ix) {
         int cur = -1;
         if (hipGetDevice(&cur) != hipSuccess || cur != ix->device) return FA_ERROR_DEVICE;
@@ -2258,26 +2268,17 @@ static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes,
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
     if (first < 0 && last < 0) { first = 0; last = stream_size; }
     if (first < 0 || last > stream_size || first >= last) return FA_ERROR_DECODE_SAMPLE_RANGE;
-    if (width < 1 || !d_min || !d_max || !d_sum || (d_sq_hi == nullptr) != (d_sq_lo == nullptr) || (nch == 2 && d_sq_hi)) return FA_ERROR_CONVERT_TYPE;
-    if (d_sel && n_sel <= 0) return n_sel == 0 ? FA_ERROR_NONE : FA_ERROR_CONVERT_TYPE;
+    return FA_ERROR_NONE;
+}
+
+// Two-channel stores: [first, last) of the rows (all streams, or the `rows` streams d_sel names) decoded in column chunks
+// of whole frames under the cap; fold(chunk, at, end) launches what folds the int64 chunk [rows][end - at] of samples
+// [at, end) into the caller's arrays, on `st`.
+static int reduce_chunks(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                         int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t rows, const int64_t* d_sel,
+                         int64_t max_temp_bytes, hipStream_t st, int verify,
+                         const std::function<int(const long long*, int64_t, int64_t)>& fold) {
     const int64_t n = last - first;
-    if (width > n) width = n;
-    const int64_t nbins = (n + width - 1) / width;
-    const int64_t rows = d_sel ? n_sel : n_stream;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    ReduceSink red;
-    red.width = width; red.nbins = nbins; red.n_sel = n_sel; red.sel = d_sel;
-    red.out.mn = reinterpret_cast<long long*>(d_min); red.out.mx = reinterpret_cast<long long*>(d_max);
-    red.out.sum = reinterpret_cast<long long*>(d_sum);
-    red.out.sq_hi = reinterpret_cast<unsigned long long*>(d_sq_hi); red.out.sq_lo = reinterpret_cast<unsigned long long*>(d_sq_lo);
-    red.out.nbins = nbins;
-    const int64_t cells = rows * nbins;
-    if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
-    hipLaunchKernelGGL(reduce_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, red.out, cells);
-    if (nch == 1)
-        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, n, -1, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr, 0,
-                                  nullptr, nullptr, nullptr, &red);
     int rc;
     int64_t B = ix ? ix->B : 0;
     if (!ix && (rc = reduce_peek_blocksize(d_bytes, n_bytes, d_starts, st, &B))) return rc;
@@ -2303,24 +2304,58 @@ static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes,
                                 nullptr, nullptr, nullptr, nullptr, st, 2, reinterpret_cast<int64_t*>(d_tmp), nullptr, nullptr, nullptr, ix, false,
                                 verify);
         if (rc) return rc;
-        if (width >= 64) {
-            const int64_t nseg = (w + kReduceSeg - 1) / kReduceSeg;
-            if (rows * nseg > 0x7fffffff) return FA_ERROR_ALLOC;
-            const dim3 grid((unsigned)(rows * nseg)), block(64);
-            hipLaunchKernelGGL(reduce_wave_kernel, grid, block, 0, st, reinterpret_cast<const long long*>(d_tmp), w, at, first, last, width, nseg, red.out);
-        } else {
-            const int64_t bin_lo = (at - first) / width, n_bin = (end - 1 - first) / width - bin_lo + 1;
-            const int64_t nblk = (n_bin + 255) / 256;
-            if (rows * nblk > 0x7fffffff) return FA_ERROR_ALLOC;
-            const dim3 grid((unsigned)(rows * nblk)), block(256);
-            hipLaunchKernelGGL(reduce_lane_kernel, grid, block, 0, st, reinterpret_cast<const long long*>(d_tmp), w, at, first, last, width, bin_lo, n_bin, nblk,
-                               red.out);
-        }
+        if ((rc = fold(reinterpret_cast<const long long*>(d_tmp), at, end))) return rc;
         at = end;
     }
     FA_HIP_TRY(hipStreamSynchronize(st));  // (the scratch is free again, the bins are complete)
     FA_HIP_TRY(hipGetLastError());
     return FA_ERROR_NONE;
+}
+
+static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                         int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel,
+                         const int64_t* d_sel, int64_t max_temp_bytes, int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi,
+                         uint64_t* d_sq_lo, void* stream, int verify) {
+    FA_API_LOCK;
+    int rc;
+    if ((rc = reduce_store_args(nch, ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last))) return rc;
+    if (width < 1 || !d_min || !d_max || !d_sum || (d_sq_hi == nullptr) != (d_sq_lo == nullptr) || (nch == 2 && d_sq_hi)) return FA_ERROR_CONVERT_TYPE;
+    if (d_sel && n_sel <= 0) return n_sel == 0 ? FA_ERROR_NONE : FA_ERROR_CONVERT_TYPE;
+    const int64_t n = last - first;
+    if (width > n) width = n;
+    const int64_t nbins = (n + width - 1) / width;
+    const int64_t rows = d_sel ? n_sel : n_stream;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ReduceSink red;
+    red.width = width; red.nbins = nbins; red.n_sel = n_sel; red.sel = d_sel;
+    red.out.mn = reinterpret_cast<long long*>(d_min); red.out.mx = reinterpret_cast<long long*>(d_max);
+    red.out.sum = reinterpret_cast<long long*>(d_sum);
+    red.out.sq_hi = reinterpret_cast<unsigned long long*>(d_sq_hi); red.out.sq_lo = reinterpret_cast<unsigned long long*>(d_sq_lo);
+    red.out.nbins = nbins;
+    const int64_t cells = rows * nbins;
+    if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
+    hipLaunchKernelGGL(reduce_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, red.out, cells);
+    if (nch == 1)
+        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, n, -1, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr, 0,
+                                  nullptr, nullptr, nullptr, &red);
+    return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, rows, d_sel, max_temp_bytes, st, verify,
+                         [&](const long long* tmp, int64_t at, int64_t end) -> int {
+        const int64_t w = end - at;
+        if (width >= 64) {
+            const int64_t nseg = (w + kReduceSeg - 1) / kReduceSeg;
+            if (rows * nseg > 0x7fffffff) return FA_ERROR_ALLOC;
+            const dim3 grid((unsigned)(rows * nseg)), block(64);
+            hipLaunchKernelGGL(reduce_wave_kernel, grid, block, 0, st, tmp, w, at, first, last, width, nseg, red.out);
+        } else {
+            const int64_t bin_lo = (at - first) / width, n_bin = (end - 1 - first) / width - bin_lo + 1;
+            const int64_t nblk = (n_bin + 255) / 256;
+            if (rows * nblk > 0x7fffffff) return FA_ERROR_ALLOC;
+            const dim3 grid((unsigned)(rows * nblk)), block(256);
+            hipLaunchKernelGGL(reduce_lane_kernel, grid, block, 0, st, tmp, w, at, first, last, width, bin_lo, n_bin, nblk, red.out);
+        }
+        return FA_ERROR_NONE;
+    });
 }
 
 int fa_reduce_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
@@ -2343,6 +2378,70 @@ int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, i
     if (!ix) return FA_ERROR_DECODE_INIT;
     return reduce_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, width, n_sel, d_sel_streams, max_temp_bytes, d_min, d_max,
                          d_sum, d_sq_hi, d_sq_lo, stream, verify);
+}
+
+// ---- value histogram: counts per value bin of every row, without a decoded copy (profiles/histogram.md) ----------------
+// One-channel streams: the histogram sink of K7 (K7H).  Two-channel streams: the column chunks of the binned reduction,
+// each counted by hist_wave_kernel.
+static int histogram_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                            int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel,
+                            int64_t max_temp_bytes, int64_t nbins, const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below,
+                            int64_t* d_above, void* stream, int verify) {
+    FA_API_LOCK;
+    int rc;
+    if ((rc = reduce_store_args(nch, ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last))) return rc;
+    if (nbins < 1 || nbins > kHistMaxBins || !d_lo || !d_shift || !d_counts || !d_below || !d_above) return FA_ERROR_CONVERT_TYPE;
+    if (d_sel && n_sel <= 0) return n_sel == 0 ? FA_ERROR_NONE : FA_ERROR_CONVERT_TYPE;
+    const int64_t rows = d_sel ? n_sel : n_stream;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HistOut ho;
+    ho.counts = reinterpret_cast<unsigned long long*>(d_counts); ho.below = reinterpret_cast<unsigned long long*>(d_below);
+    ho.above = reinterpret_cast<unsigned long long*>(d_above);
+    ho.lo = reinterpret_cast<const long long*>(d_lo); ho.shift = d_shift; ho.nbins = nbins;
+    const int64_t cells = rows * nbins;
+    if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
+    hipLaunchKernelGGL(hist_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, ho, rows);
+    if (nch == 1) {
+        ReduceSink red;
+        red.width = last - first; red.nbins = nbins; red.n_sel = n_sel; red.sel = d_sel;
+        red.out = ReduceOut{nullptr, nullptr, nullptr, nullptr, nullptr, nbins};
+        red.hist = &ho;
+        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last - first, -1, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr,
+                                  0, nullptr, nullptr, nullptr, &red);
+    }
+    return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, rows, d_sel, max_temp_bytes, st, verify,
+                         [&](const long long* tmp, int64_t at, int64_t end) -> int {
+        const int64_t w = end - at;
+        const int64_t nseg = (w + kReduceSeg - 1) / kReduceSeg;
+        if (rows * nseg > 0x7fffffff) return FA_ERROR_ALLOC;
+        hipLaunchKernelGGL(hist_wave_kernel, dim3((unsigned)(rows * nseg)), dim3(64), 0, st, tmp, w, nseg, ho);
+        return FA_ERROR_NONE;
+    });
+}
+
+int fa_histogram_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t nbins,
+                            const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below, int64_t* d_above, void* stream,
+                            int verify) {
+    return histogram_device(1, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_sel_streams, 0, nbins, d_lo,
+                            d_shift, d_counts, d_below, d_above, stream, verify);
+}
+
+int fa_histogram_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                            int64_t nbins, const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below, int64_t* d_above,
+                            void* stream, int verify) {
+    return histogram_device(2, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_sel_streams, max_temp_bytes,
+                            nbins, d_lo, d_shift, d_counts, d_below, d_above, stream, verify);
+}
+
+int fa_histogram_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes, int64_t nbins,
+                         const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below, int64_t* d_above, void* stream, int verify) {
+    DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
+    if (!ix) return FA_ERROR_DECODE_INIT;
+    return histogram_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, n_sel, d_sel_streams, max_temp_bytes, nbins, d_lo, d_shift,
+                            d_counts, d_below, d_above, stream, verify);
 }
 
 // ---- damage map and salvage decode (scrub_kernels.hpp) ----

@@ -1404,6 +1404,113 @@ def reduce_flac_device(compressed, starts, nbytes, stream_size, width=None, firs
     return mn, mx, sm, qh, ql
 
 
+def _histogram_args(rows, lo, shift, nbins):
+    """The argument checks of the value histogram (ValueError, before anything touches the GPU): `nbins` in 1..2048, `lo`
+    and `shift` Python integers or integer arrays / tensors of length `rows`, lo inside int64, shift in 0..63.  Returns
+    (nbins, lo as int64[rows], shift as int32[rows]) numpy arrays."""
+    torch = _torch()
+    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= int(nbins) <= 2048:
+        raise ValueError("nbins should be an integer in 1..2048")
+
+    def column(v, name, vmin, vmax, dt):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v)
+        if a.dtype == object:
+            if not all(isinstance(e, (int, np.integer)) and not isinstance(e, bool) for e in a.reshape(-1)):
+                raise ValueError(f"{name} should hold integers")
+        elif a.dtype.kind not in "iu":
+            raise ValueError(f"{name} should be an integer or an integer array")
+        if a.ndim > 1 or (a.ndim == 1 and a.size != rows):
+            raise ValueError(f"{name} should be one integer or {rows} of them, one per row")
+        if a.size and (min(int(e) for e in a.reshape(-1)) < vmin or max(int(e) for e in a.reshape(-1)) > vmax):
+            raise ValueError(f"{name} holds a value outside [{vmin}, {vmax}]")
+        return np.array(np.broadcast_to(a.astype(dt), (rows,)))  # (a copy: writable and contiguous)
+
+    return int(nbins), column(lo, "lo", -(1 << 63), (1 << 63) - 1, np.int64), column(shift, "shift", 0, 63, np.int32)
+
+
+def histogram_flac_device(compressed, starts, nbytes, stream_size, lo, shift, nbins, first_sample=0, last_sample=None, streams=None,
+                          is_int64=False, verify=None, max_temp_bytes=None):
+    """Counts per value bin of what device-resident streams decode to, without a decoded copy (fa_histogram_i32_device /
+    fa_histogram_i64_device).  Samples [first_sample, last_sample) (default: everything) of every stream, or of the
+    streams that `streams` names (rows in that order), are counted in `nbins` (1..2048) bins per row: a sample x of row r
+    below lo[r] counts in below[r]; otherwise its bin is ((uint64)x - (uint64)lo[r]) >> shift[r], counted in
+    counts[r, bin] or, from nbins on, in above[r].  `lo` (int64) and `shift` (0..63) are Python integers or integer
+    arrays / tensors of length rows.  counts.sum(-1) + below + above == last_sample - first_sample for every row.
+
+    Returns (counts [rows, nbins], below [rows], above [rows]): int64 device tensors over the decoded INTEGERS (for a
+    float store the quantised ones); an empty `streams` returns shapes (0, nbins), (0,), (0,).
+
+    One-channel streams are counted inside the decoder (K7H): a wave whose 64 frames belong to one row counts in a
+    histogram in LDS and adds its non-zero words to `counts` once; a wave that holds several rows (streams shorter than
+    64 frames) adds every sample straight to `counts`, which is correct and slow.  Two-channel streams go through decoded
+    column chunks of whole frames under `max_temp_bytes` (default 256 MiB), as reduce_flac_device's do.  At 4096 x 2^20
+    int32 a call takes 8.6 ms at any bin count (the bare decode: 6.6 ms) and 15.8 ms when every sample falls into one
+    bin; at 1024 x 2^20 int64, 54-56 ms against 10.6 ms for the bare decode (profiles/histogram.md).  `verify` is the decoder's frame CRC-16 check; argument errors raise ValueError before
+    any GPU work, decode failures the decoder's RuntimeError.  Streams of several block sizes go one block size at a
+    time."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64:
+        raise ValueError("starts and nbytes should be of type int64")
+    if starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes must have the same shape")
+    n_stream = int(np.prod(starts.shape))
+    if n_stream <= 0:
+        raise ValueError("starts needs at least one stream")
+    first, last, _, _, idx = _reduce_args(n_stream, stream_size, None, first_sample, last_sample, streams)
+    rows = n_stream if idx is None else int(idx.size)
+    nbins, lo_h, shift_h = _histogram_args(rows, lo, shift, nbins)
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("histogram_flac_device needs compressed, starts and nbytes on the same GPU")
+    counts = torch.empty((rows, nbins), dtype=torch.int64, device=dev)
+    below = torch.empty((rows,), dtype=torch.int64, device=dev)
+    above = torch.empty((rows,), dtype=torch.int64, device=dev)
+    if rows == 0:
+        return counts, below, above
+    sel = None if idx is None else torch.from_numpy(idx).to(dev)
+    d_lo, d_shift = torch.from_numpy(lo_h).to(dev), torch.from_numpy(shift_h).to(dev)
+    cap = 0 if max_temp_bytes is None else int(max_temp_bytes)
+    L = _lib.lib()
+    with _on_device(dev):
+        if is_int64:
+            errcode = L.fa_histogram_i64_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                                rows, _dp(sel), cap, nbins, _dp(d_lo), _dp(d_shift), _dp(counts), _dp(below), _dp(above),
+                                                _stream_ptr(), _verify_arg(verify))
+        else:
+            errcode = L.fa_histogram_i32_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                                rows, _dp(sel), nbins, _dp(d_lo), _dp(d_shift), _dp(counts), _dp(below), _dp(above),
+                                                _stream_ptr(), _verify_arg(verify))
+    if errcode != 0:
+        # streams of different block sizes: one call per block size (see _blocksize_classes), rows scattered back
+        st, nb = starts.reshape(-1), nbytes.reshape(-1)
+        groups = None
+        if n_stream > 1 and bool(((st >= 0) & (nb >= 12) & (st + nb <= compressed.numel())).all()):
+            groups = _blocksize_classes(compressed[st[:, None] + torch.arange(12, device=dev)[None, :]].cpu().numpy())
+        if groups is None:
+            raise RuntimeError(f"Decoding failed, return code = {errcode}")
+        for g in groups:
+            if idx is None:
+                at, local = g, None
+            else:
+                at = np.flatnonzero(np.isin(idx, g))  # rows of the result that name a stream of this class
+                if at.size == 0:
+                    continue
+                local = np.searchsorted(g, idx[at])
+            gi = torch.from_numpy(g).to(dev)
+            part = histogram_flac_device(compressed, st[gi].contiguous(), nb[gi].contiguous(), stream_size, lo_h[at], shift_h[at], nbins, first,
+                                         last, streams=local, is_int64=is_int64, verify=verify, max_temp_bytes=max_temp_bytes)
+            ai = torch.from_numpy(at).to(dev)
+            for out, p in zip((counts, below, above), part):
+                out[ai] = p
+    return counts, below, above
+
+
 class DeviceDecodeIndex:
     """Decode index of one HBM-resident store (fa_decode_index_create): the stream headers are parsed and the byte
     offset of every frame is tabulated ONCE; `decode` / `decode_slices` then cost one kernel launch each.  Holds
@@ -1491,6 +1598,28 @@ class DeviceDecodeIndex:
         if errcode != 0:
             raise RuntimeError(f"Decoding failed, return code = {errcode}")
         return mn, mx, sm, qh, ql
+
+    def histogram(self, lo, shift, nbins, first_sample=0, last_sample=None, streams=None, verify=None, max_temp_bytes=None):
+        """histogram_flac_device on the indexed store (fa_histogram_indexed): nothing is parsed again.  Returns (counts
+        [rows, nbins], below [rows], above [rows]), int64 tensors."""
+        torch = _torch()
+        first, last, _, _, idx = _reduce_args(self.n_stream, self.stream_size, None, first_sample, last_sample, streams)
+        rows = self.n_stream if idx is None else int(idx.size)
+        nbins, lo_h, shift_h = _histogram_args(rows, lo, shift, nbins)
+        counts = torch.empty((rows, nbins), dtype=torch.int64, device=self.device)
+        below = torch.empty((rows,), dtype=torch.int64, device=self.device)
+        above = torch.empty((rows,), dtype=torch.int64, device=self.device)
+        if rows == 0:
+            return counts, below, above
+        sel = None if idx is None else torch.from_numpy(idx).to(self.device)
+        d_lo, d_shift = torch.from_numpy(lo_h).to(self.device), torch.from_numpy(shift_h).to(self.device)
+        with _on_device(self.device):
+            errcode = self._L.fa_histogram_indexed(self._h, first, last, rows, _dp(sel), 0 if max_temp_bytes is None else int(max_temp_bytes),
+                                                   nbins, _dp(d_lo), _dp(d_shift), _dp(counts), _dp(below), _dp(above), _stream_ptr(),
+                                                   _verify_arg(verify))
+        if errcode != 0:
+            raise RuntimeError(f"Decoding failed, return code = {errcode}")
+        return counts, below, above
 
     def decode_slices(self, slice_stream, slice_first, slice_count, offsets=None, gains=None, verify=None, to_host=False):
         """Batched random access (see decode_slices_device): returns (flat tensor, int64 numpy array of offsets);

@@ -413,6 +413,27 @@ int fa_reduce_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const in
 int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
                       int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
 
+/* ---- value histogram: counts per value bin of what the streams decode to, without a decoded copy.  Store, range, rows
+ * (d_sel_streams / n_sel), max_temp_bytes, `verify`, errors and stream ordering are fa_reduce_*'s.  Every row r has its own
+ * d_lo[r] (int64) and d_shift[r] (int32, 0..63), DEVICE arrays of `rows` elements; the call has one nbins, 1..2048
+ * (otherwise FA_ERROR_CONVERT_TYPE).  A sample x of row r with x < d_lo[r] counts in d_below[r]; otherwise its bin is
+ * b = ((uint64)x - (uint64)d_lo[r]) >> d_shift[r] (the unsigned difference is exact for every x >= lo), counted in
+ * d_counts[r * nbins + b] when b < nbins and in d_above[r] otherwise: counts + below + above of a row is last - first.
+ * Outputs are int64 device arrays, [rows][nbins] and [rows]; the call zeroes them on `stream` first.  One-channel streams
+ * are counted inside the decoder (K7H: a per-wave histogram in LDS where the storing decoder keeps its tile image);
+ * two-channel streams go through the decoded column chunks of fa_reduce_i64_device.  What is counted is what any FLAC
+ * decoder produces -- for float stores the quantised integers (profiles/histogram.md). ---- */
+int fa_histogram_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t nbins,
+                            const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below, int64_t* d_above, void* stream,
+                            int verify);
+int fa_histogram_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                            int64_t nbins, const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below, int64_t* d_above,
+                            void* stream, int verify);
+int fa_histogram_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes, int64_t nbins,
+                         const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below, int64_t* d_above, void* stream, int verify);
+
 /* ---- damage map and decode through errors.  The decode, compare, reduce and MD5 entry points give up a whole call for one
  * bad frame; these answer per (stream, frame), from nothing but the store, and decode what is intact.
  * fa_frame_status_device writes d_status[n_stream][nf] (device, one byte each), nf = ceil(stream_size / block_size):
