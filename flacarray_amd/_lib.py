@@ -100,6 +100,8 @@ SYMBOLS = [
     "fa_profile_last",
     "fa_profile_read",
     "fa_release_scratch",
+    "fa_debug_scratch_fill",
+    "fa_debug_scratch_bytes",
     "fa_device_count",
     "fa_version",
     "fa_abi_version",
@@ -287,6 +289,11 @@ def lib():
     L.fa_profile_read.restype = cint
     L.fa_release_scratch.argtypes = []
     L.fa_release_scratch.restype = None
+    if hasattr(L, "fa_debug_scratch_fill") or not os.environ.get("FLACARRAY_HIP_LIB"):  # (test-only; an older A/B build lacks them)
+        L.fa_debug_scratch_fill.argtypes = [cint]
+        L.fa_debug_scratch_fill.restype = cint
+        L.fa_debug_scratch_bytes.argtypes = [pi64, cint]
+        L.fa_debug_scratch_bytes.restype = cint
     L.fa_device_count.argtypes = []
     L.fa_device_count.restype = cint
     L.fa_version.argtypes = []

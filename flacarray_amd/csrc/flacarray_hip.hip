@@ -88,6 +88,7 @@ struct DeviceState {
     // (stream_size, chunk) whose summation plans scratch[13] holds, valid while scratch_epoch == std_plan_epoch
     int64_t std_plan_key[2] = {-1, -1};
     uint64_t std_plan_epoch = 0;
+    int debug_fill = -1;  // fa_debug_scratch_fill: the byte every newly allocated slot is filled with, -1 = none (the default)
     hipStream_t feed_stream = nullptr;  // the host entry points' upload stream (created once: a new stream costs tens of ms)
     // small reads that want their samples on the host: the latency decoder stores them (and its status word) straight
     // into this pinned, device-visible buffer -- no copy calls, one stream synchronisation (decode_device_impl)
@@ -167,6 +168,9 @@ int get_scratch(int slot, size_t bytes, void** out) {
             want = bytes;
         }
         st->scratch_bytes[slot] = want;
+        if (st->debug_fill >= 0) {  // fa_debug_scratch_fill (tests): a fresh slot starts as dirty as the held ones
+            if (hipMemset(st->scratch[slot], st->debug_fill, want) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return FA_ERROR_DEVICE;
+        }
     }
     *out = st->scratch[slot];
     return FA_ERROR_NONE;
@@ -1152,6 +1156,32 @@ void fa_release_scratch(void) {
     if (ds_->pin) (void)hipHostFree(ds_->pin);
     ds_->pin = ds_->pin_dev = nullptr;
     ds_->pin_tried = false;
+}
+
+// test-only: make every scratch slot dirty on purpose.  byte in 0..255 fills every held slot over its whole allocation
+// and is remembered, so that a slot get_scratch allocates later starts filled too; -1 turns that off again (and fills
+// nothing).  Either way the epoch moves on: the header table and the std plans live in slots and are no longer trusted.
+int fa_debug_scratch_fill(int byte) {
+    if (byte < -1 || byte > 255) return FA_ERROR_ALLOC;
+    FA_API_LOCK;
+    FA_HIP_TRY(hipDeviceSynchronize());
+    ds_->debug_fill = byte;
+    if (byte >= 0) {
+        for (int i = 0; i < kScratchSlots; ++i)
+            if (ds_->scratch[i]) FA_HIP_TRY(hipMemset(ds_->scratch[i], byte, ds_->scratch_bytes[i]));
+        FA_HIP_TRY(hipDeviceSynchronize());
+    }
+    ds_->scratch_epoch++;
+    ds_->stamps_zeroed = false;
+    return FA_ERROR_NONE;
+}
+
+// test-only: out[i] = bytes slot i holds now, for i < min(n, kScratchSlots) (zeros without a device); returns kScratchSlots
+int fa_debug_scratch_bytes(int64_t* out, int n) {
+    for (int i = 0; i < n && i < kScratchSlots; ++i) out[i] = 0;
+    FA_API_LOCK_OR(return kScratchSlots);
+    for (int i = 0; i < n && i < kScratchSlots; ++i) out[i] = (int64_t)ds_->scratch_bytes[i];
+    return kScratchSlots;
 }
 
 static int64_t slot_workspace_for(int64_t n_stream, int64_t stream_size, uint32_t level, int nch) {

@@ -633,6 +633,15 @@ int fa_profile_read(float* ms, int n);
 /* free the library's cached device scratch (decode tables, staging buffers) */
 void fa_release_scratch(void);
 
+/* Diagnostic, for the test suite only (no library code, tool or benchmark calls them).
+ * fa_debug_scratch_fill(byte), byte in 0..255: waits for the device, fills every cached scratch slot over its whole
+ * allocation with `byte`, drops what the library caches inside slots (the encoders' frame-header table, the std
+ * summation plans), and from then on fills every slot it allocates with `byte` as well.  byte = -1 turns that sticky fill
+ * off again (the default).  FA_ERROR_ALLOC for any other value.
+ * fa_debug_scratch_bytes(out, n): out[i] = the bytes slot i holds now, i < min(n, slots); returns the number of slots. */
+int fa_debug_scratch_fill(int byte);
+int fa_debug_scratch_bytes(int64_t* out, int n);
+
 /* number of visible HIP devices (0 when there is no GPU); never initialises a context */
 int fa_device_count(void);
 
