@@ -839,11 +839,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
                 const int4 h7 = *reinterpret_cast<const int4*>(&smp[hist7]), h6 = *reinterpret_cast<const int4*>(&smp[hist6]);
                 const int4 h5 = *reinterpret_cast<const int4*>(&smp[hist5]);
                 const int hs[12] = {h7.w, h7.z, h7.y, h7.x, h6.w, h6.z, h6.y, h6.x, h5.w, h5.z, h5.y, h5.x};
+                // the window values of the history: whole 16-byte units in front of the lane's chunk, loaded without a
+                // condition so that they are in flight together with the first batch below (a guarded scalar load per
+                // value is an exec region and a full memory wait each).  Lane 0 has no window in front of it and reads
+                // the first units instead: its history samples are the zero chunk, and 0 times a finite non-negative
+                // window value is the +0.0 that 0 * 0.0f was.
+                const int gh = max(g0, 16);
+                const float4 wh0 = *reinterpret_cast<const float4*>(win + gh - 4), wh1 = *reinterpret_cast<const float4*>(win + gh - 8);
+                float4 wh2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if constexpr (MLO > 8) wh2 = *reinterpret_cast<const float4*>(win + gh - 12);
+                const float whs[12] = {wh0.w, wh0.z, wh0.y, wh0.x, wh1.w, wh1.z, wh1.y, wh1.x, wh2.w, wh2.z, wh2.y, wh2.x};
 #pragma unroll
-                for (int j = 0; j < MLO; ++j) {
-                    const float wh = (g0 - 1 - j >= 0) ? win[g0 - 1 - j] : 0.0f;
-                    hist[j] = (double)hs[j] * (double)wh;
-                }
+                for (int j = 0; j < MLO; ++j) hist[j] = (double)hs[j] * (double)whs[j];
                 // window values four groups at a time (16 registers in flight, not 32: the kernel lives at 168)
 #pragma unroll
                 for (int tb = 0; tb < 8; tb += FA_F_WBATCH) {
@@ -1305,13 +1312,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
     // One Rice code whose stop bit lands at stream bit P: the stop bit and the k low bits of u, left-aligned in a word
     // (shl = 31 - k; whatever u holds above bit k is shifted out or falls on the stop bit), then funnel-shifted to
     // P mod 32 -- v_alignbit takes the shift modulo 32, so there is no mask, no 64-bit shift and no subtraction.
-    auto put_code = [&](uint32_t P, uint32_t u, uint32_t shl) __attribute__((always_inline)) {
-        const uint32_t vL = (u << shl) | 0x80000000u;
+    // put_left takes the left-aligned word itself (bit 31 lands at P); a zero word writes nothing.
+    auto put_left = [&](uint32_t P, uint32_t vL) __attribute__((always_inline)) {
         uint32_t wi;  // (asm: the compiler rewrites the bit-field extract into shift + mask and then needs a separate add)
         asm("v_bfe_u32 %0, %1, 5, %2" : "=v"(wi) : "v"(P), "n"(__builtin_ctz((unsigned)kFRingWords)));
         uint32_t* const w = ring + wi;
         atomicOr(w, __builtin_amdgcn_alignbit(0u, vL, P));
         atomicOr(w + 1, __builtin_amdgcn_alignbit(vL, 0u, P));  // may be the mirror word
+    };
+    auto put_code = [&](uint32_t P, uint32_t u, uint32_t shl) __attribute__((always_inline)) {
+        put_left(P, (u << shl) | 0x80000000u);
     };
     // byte offset of the frame: the scanner stores it in off_pub[g] once every frame before it has published.
     // lb_issue reads the word once (usually still zero); lb_resolve, where the first block is about to leave the
@@ -1632,11 +1642,84 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
                 }
                 pos += total;
             };
-            row8(std::true_type{}, 0);
+            // The same row where a partition is at least a row long (porder <= 3, the usual case): the row has ONE Rice
+            // parameter, read from the register that holds the partitions' parameters (lane p: partition p) into a
+            // scalar, and a partition can open only at the row's first bit.  So its parameter field is the row's
+            // business, not a lane's: the wave knows from j whether there is one, its length joins the row total as a
+            // scalar and lane 0 writes it at `pos`; the lanes' codes follow it.  No table look-up, no per-lane
+            // partition test, and a row without a field executes nothing for it.  Row 0 goes the same way: a warm-up
+            // sample is a code of no bits (put_left with a zero word) that moves the position by nothing.
+            auto row8u = [&](auto first_tag, int j) __attribute__((always_inline)) {
+                constexpr bool FIRST = decltype(first_tag)::value;
+                const uint32_t rb = (uint32_t)(512 * j);
+                const int4 va = *reinterpret_cast<const int4*>(&smp[r8a + 512 * (j & 3)]);
+                const int4 vb = *reinterpret_cast<const int4*>(&smp[r8b + 512 * (j & 3)]);
+                const uint32_t us[8] = {(uint32_t)va.x, (uint32_t)va.y, (uint32_t)va.z, (uint32_t)va.w,
+                                        (uint32_t)vb.x, (uint32_t)vb.y, (uint32_t)vb.z, (uint32_t)vb.w};
+                const uint32_t k = (uint32_t)__builtin_amdgcn_readlane(kbest, (int)(rb >> l2ps)), kp1 = k + 1u;
+                const uint32_t fld = (FIRST || (rb & (ps - 1u)) == 0u) ? (uint32_t)plen : 0u;
+                uint32_t q[8], adv[8];
+                uint32_t len = 0;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const uint32_t qq = us[e] >> k;
+                    if constexpr (FIRST) {
+                        const bool valid = (uint32_t)(8 * lane_w + e) >= (uint32_t)order;
+                        q[e] = valid ? qq : 0u;
+                        adv[e] = valid ? (qq + kp1) : 0u;
+                        len += adv[e];
+                    } else {
+                        q[e] = qq;
+                        len += qq;
+                    }
+                }
+                const uint32_t lane_len = FIRST ? len : (len + 8u * kp1);
+                const uint32_t incl = wave_incl_scan_u32(lane_len);
+                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63) + fld;
+#ifdef FA_STAMPS
+                const unsigned long long tf0_ = fa_memtime();
+#endif
+                flush_blocks(total, false);
+#ifdef FA_STAMPS
+                st_[15] += fa_memtime() - tf0_;  // (part of "rows": the flush calls)
+#endif
+                uint32_t p = pos + fld + incl - lane_len;
+                // (the shift count lives in a vector register: shift-and-or takes ONE scalar operand, and the stop bit
+                // is it -- with a scalar count the instruction splits in two, eight times a row)
+                uint32_t shl = 31u - k;
+                asm("" : "+v"(shl));
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    if constexpr (FIRST) {
+                        put_left(p + q[e], adv[e] ? ((us[e] << shl) | 0x80000000u) : 0u);
+                        p += adv[e];
+                    } else {
+                        put_code(p + q[e], us[e], shl);
+                        p += q[e] + kp1;
+                    }
+                }
+                if (fld != 0u) {
+                    // (the empty statement keeps this a branch of the wave: without it the compiler folds the test into
+                    // the lane's condition and every row pays an exec region for a field that one row in eight has)
+                    asm volatile("");
+                    if (lane_w == 0) put_bits(pos, k, (uint32_t)plen);
+                }
+                pos += total;
+            };
+            if (__builtin_expect(porder <= 3, 1)) {
+                row8u(std::true_type{}, 0);
 #pragma unroll 1
-            for (int j = 1; j < 8; ++j) {
-                if (j == 4) store_b();  // rows 0..3 (the first half) have been read: the second half takes their place
-                row8(std::false_type{}, j);
+                for (int j = 1; j < 8; ++j) {
+                    if (j == 4) store_b();  // rows 0..3 (the first half) have been read: the second half takes their place
+                    row8u(std::false_type{}, j);
+                }
+            } else {
+                row8(std::true_type{}, 0);
+#pragma unroll 1
+                for (int j = 1; j < 8; ++j) {
+                    if (j == 4) store_b();
+                    row8(std::false_type{}, j);
+                }
             }
         }
     }
