@@ -6,7 +6,7 @@ Drop-in names of the reference (hpc4cmb/flacarray): `array_compress`, `array_dec
 BASELINE.json.  All compute runs in hand-written HIP kernels (libflacarray_hip.so); there is
 no CPU fallback.
 """
-from .array import FlacArray, StreamHistogram, StreamStats
+from .array import FlacArray, StreamHistogram, StreamHits, StreamStats
 from .compress import array_compress
 from .decompress import array_decompress, array_decompress_slice
 from .libflacarray import (
@@ -30,6 +30,8 @@ from .libflacarray import (
     overwrite_flac_device,
     reduce_flac_device,
     histogram_flac_device,
+    find_flac_device,
+    find_counts_flac_device,
     reindex_flac_device,
     set_decode_verify,
     set_encode_md5,
@@ -49,6 +51,7 @@ __version__ = "0.1.0"
 __all__ = [
     "FlacArray",
     "StreamHistogram",
+    "StreamHits",
     "StreamStats",
     "DeviceDecodeIndex",
     "append_flac_device",
@@ -78,6 +81,8 @@ __all__ = [
     "compare_flac_device",
     "reduce_flac_device",
     "histogram_flac_device",
+    "find_flac_device",
+    "find_counts_flac_device",
     "md5_device",
     "check_md5_device",
     "sign_streams_device",

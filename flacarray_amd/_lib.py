@@ -77,6 +77,14 @@ SYMBOLS = [
     "fa_histogram_i32_device",
     "fa_histogram_i64_device",
     "fa_histogram_indexed",
+    "fa_find_plan_device",
+    "fa_find_plan_indexed",
+    "fa_find_count_i32_device",
+    "fa_find_count_i64_device",
+    "fa_find_count_indexed",
+    "fa_find_fill_i32_device",
+    "fa_find_fill_i64_device",
+    "fa_find_fill_indexed",
     "fa_frame_status_device",
     "fa_fill_ranges_device",
     "fa_decode_salvage_i32_device",
@@ -256,6 +264,22 @@ def lib():
     L.fa_histogram_i64_device.restype = cint
     L.fa_histogram_indexed.argtypes = [vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, cint]
     L.fa_histogram_indexed.restype = cint
+    L.fa_find_plan_device.argtypes = [vp, i64, vp, i64, i64, i64, vp, vp, vp]
+    L.fa_find_plan_device.restype = cint
+    L.fa_find_plan_indexed.argtypes = [vp, i64, i64, vp, vp]
+    L.fa_find_plan_indexed.restype = cint
+    L.fa_find_count_i32_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, cint, i64, vp, vp, cint]
+    L.fa_find_count_i32_device.restype = cint
+    L.fa_find_count_i64_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp, cint, i64, vp, vp, cint]
+    L.fa_find_count_i64_device.restype = cint
+    L.fa_find_count_indexed.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, cint, i64, vp, vp, cint]
+    L.fa_find_count_indexed.restype = cint
+    L.fa_find_fill_i32_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, cint, i64, i64, vp, vp, vp, vp, vp, cint]
+    L.fa_find_fill_i32_device.restype = cint
+    L.fa_find_fill_i64_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp, cint, i64, i64, vp, vp, vp, vp, vp, cint]
+    L.fa_find_fill_i64_device.restype = cint
+    L.fa_find_fill_indexed.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, cint, i64, i64, vp, vp, vp, vp, vp, cint]
+    L.fa_find_fill_indexed.restype = cint
     L.fa_frame_status_device.argtypes = [vp, i64, vp, vp, i64, i64, cint, i64, vp, vp]
     L.fa_frame_status_device.restype = cint
     L.fa_fill_ranges_device.argtypes = [vp, cint, i64, vp, vp, vp, vp]

@@ -503,13 +503,13 @@ struct DecodeArgs {
     // outputs.  (The unions: the reducing sink, which has no use for the store's, the restore's, the two-channel image's or
     // the compare sink's arguments, keeps its own in their places -- the layout, and with it the code of every other
     // instantiation, is what it was without that sink.)
-    union { int32_t* out_i32; long long* red_min; unsigned long long* hist_counts; };
-    union { float* out_f32; long long* red_max; unsigned long long* hist_below; };                 // when non-null: dequantised output instead of out_i32
-    union { const float* offsets; long long* red_sum; unsigned long long* hist_above; };           // per stream
-    union { const float* gains; unsigned long long* red_sq_hi; const long long* hist_lo; };
+    union { int32_t* out_i32; long long* red_min; unsigned long long* hist_counts; long long* find_out; };
+    union { float* out_f32; long long* red_max; unsigned long long* hist_below; long long* find_val; };                 // when non-null: dequantised output instead of out_i32
+    union { const float* offsets; long long* red_sum; unsigned long long* hist_above; const long long* find_lo; };           // per stream
+    union { const float* gains; unsigned long long* red_sq_hi; const long long* hist_lo; const long long* find_hi; };
     int* err;
     // two-channel arrays (NCH == 2): out_i32 is then the task-local planar image
-    union { uint32_t* hibits; unsigned long long* red_sq_lo; const int32_t* hist_shift; };   // [n_tasks][2][hib_words] bit 32 of every sample
+    union { uint32_t* hibits; unsigned long long* red_sq_lo; const int32_t* hist_shift; const long long* find_ids; };   // [n_tasks][2][hib_words] bit 32 of every sample
     int32_t* assign;    // [n_tasks] channel assignment once both subframes are decoded, else -1
     int32_t hib_words;  // ceil(B / 32)
     int32_t verbatim_done;  // NCH == 2: VERBATIM first subframes (no wasted bits) were decoded by verbatim_channel0_kernel
@@ -526,9 +526,17 @@ struct DecodeArgs {
     // bins per row (1..2048).  A sample x of row r below hist_lo[r] counts in hist_below[r]; otherwise its bin is
     // ((uint64)x - (uint64)hist_lo[r]) >> hist_shift[r], counted in hist_counts[r * red_nbins + bin] or, from red_nbins
     // on, in hist_above[r].  The three arrays hold zeros before the launch; red_width is not used.
-    union { const void* cmp; int64_t red_width; };
-    union { unsigned long long* first_mismatch; int64_t red_nbins; };
+    // search sink (decode_frames_kernel<..., FIND = 1 | 2>; one channel), K7F: a sample x of row r is a hit iff
+    // (x < find_lo[r] || x > find_hi[r]) != (find_inside != 0).  Count pass (FIND = 1): the lane that decodes frame f of row
+    // r stores its number of hits to find_out[r * nfr + (f - f0)] (red_nbins holds nfr, so that out_off is r * nfr as for
+    // the other folding sinks).  Fill pass (FIND = 2, list mode only): task t is cell find_ids[t] = r * nfr + (f - f0) of
+    // that array; its k-th hit goes to find_out[base + k] (the sample's index in the stream) and, when find_val is not
+    // null, find_val[base + k] (its value), base = task_out_off[t] = find_offs[find_ids[t]], the exclusive prefix sum of
+    // the counts (cells + 1 entries); a lane writes at most find_offs[id + 1] - find_offs[id] hits.
+    union { const void* cmp; int64_t red_width; int64_t find_inside; };
+    union { unsigned long long* first_mismatch; int64_t red_nbins; const long long* find_offs; };
 };
+static_assert(sizeof(DecodeArgs) == 216, "DecodeArgs: the sinks share the unions, the layout of the storing decoder's arguments stays");
 
 // ------------------------------------------------------------------------------------------
 // K7 (v2).  One wavefront = 64 frames, one LANE per frame, all lanes in lockstep on the sample
@@ -801,7 +809,12 @@ __device__ __noinline__ BitsRet slow_sample(const uint8_t* cbase, const uint8_t*
 // non-zero words to hist_counts when its frames are done; a wave that holds several rows (short streams, the seam
 // between two streams) adds every sample straight to hist_counts.  Both use 64-bit relaxed atomics of agent scope:
 // integer adds commute, so the counts do not depend on the order of arrival.
-template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false, bool HIST = false>
+// FIND (one channel, integers): the search sink, K7F.  Where the reducing sink folds a sample, this one tests it against
+// its row's limits (DecodeArgs: find_*).  FIND = 1 counts: the hits of the lane's frame add up in a register and leave
+// with one plain 8-byte store per frame, by the one pass that decodes the frame.  FIND = 2 fills: the lane writes the
+// position (and value) of its k-th hit behind its frame's base.  Hits are rare in what this is for, so the fill tests
+// __any(hit) before its divergent stores; no atomics in either, so nothing depends on the order of arrival.
+template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false, bool HIST = false, int FIND = 0>
 #ifndef FA_K7_WAVES_ATTR
 #define FA_K7_WAVES_ATTR
 #endif
@@ -814,10 +827,11 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     static_assert(NCH == 1 || (kTileW == 32 && !F32), "two-channel variant: 32-sample tiles, integer output");
     static_assert(!RED || (NCH == 1 && !F32 && !CMP), "reducing sink: one channel, integer domain");
     static_assert(!HIST || (NCH == 1 && !F32 && !CMP && !RED), "histogram sink: one channel, integer domain");
-    constexpr bool FOLD = RED || HIST;  // no tile image, no cooperative store: every sample goes to the sink from its register
+    static_assert(FIND == 0 || (NCH == 1 && !F32 && !CMP && !RED && !HIST), "search sink: one channel, integer domain");
+    constexpr bool FOLD = RED || HIST || FIND != 0;  // no tile image, no cooperative store: every sample goes to the sink from its register
     constexpr bool SINK = CMP && NCH == 1;  // the tile store compares instead of writing
     // one LDS object, so that the ring image starts at LDS address 0 (ring_words builds its addresses with an OR)
-    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + (HIST ? kHistMaxBins : RED ? 0 : kTileW * kLaneStride) + (F32 ? 128 : 0)];
+    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + (HIST ? kHistMaxBins : (RED || FIND != 0) ? 0 : kTileW * kLaneStride) + (F32 ? 128 : 0)];
     uint32_t* const rings = lds_k7;
     int32_t* const tile = reinterpret_cast<int32_t*>(lds_k7 + kDecRingWords * kLaneStride);  // sample t of lane l at t*64 + (l ^ 8*(t>>2))
     float2* const row_fg = reinterpret_cast<float2*>(lds_k7 + kDecRingWords * kLaneStride + kTileW * kLaneStride);
@@ -868,6 +882,26 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             for (uint32_t b = (uint32_t)lane; b < hist_nb; b += 64) hist[b] = 0u;
         }
         __syncthreads();  // (the workgroup is this wave)
+    }
+    // K7F: the lane's limits, its hits so far, how many it may write (fill) and whether this pass decodes its frame (count)
+    long long find_l = 0, find_h = 0;
+    uint32_t find_n = 0, find_cap = 0;
+    bool find_mine = false;
+    const bool find_in = FIND != 0 && a.find_inside != 0;
+    if constexpr (FIND != 0) {
+        if (has_task) {
+            int64_t row;
+            if constexpr (FIND == 2) {
+                // (find_tasks_kernel gives a cell outside the array an empty range: nothing of it is looked up)
+                const long long id = sl_last > sl_first ? a.find_ids[task] : 0;
+                row = id / a.nfr;
+                find_cap = sl_last > sl_first ? (uint32_t)(a.find_offs[id + 1] - a.find_offs[id]) : 0u;
+            } else {
+                row = a.task_stream ? out_off / a.red_nbins : s;
+            }
+            find_l = a.find_lo[row];
+            find_h = a.find_hi[row];
+        }
     }
     // a frame the decoder rejects: the error word, or (compare sink) a mismatch at the frame's first sample
     auto reject = [&]() __attribute__((always_inline)) {
@@ -1077,6 +1111,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
             if (h2 > bs) h2 = bs;
             lo = (int)l;
             hi = (int)(h2 > l ? h2 : l);
+            if constexpr (FIND == 1) find_mine = true;  // (not deferred, not done by an earlier pass, not rejected)
             if constexpr (RED) {
                 if (hi > lo) {  // the bin of the lane's first sample, and where it ends in this frame
                     const int64_t g = fstart - sl_first;  // (frame start in range coordinates; may be negative)
@@ -1287,6 +1322,23 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         }
     };
 
+    // search sink: sample i of the lane's frame (wasted bits not yet restored) against the row's limits
+    auto find_take = [&](int i, int32_t x0) __attribute__((always_inline)) {
+        const long long x = (long long)(int32_t)((uint32_t)x0 << wasted);
+        const bool hit = ((uint32_t)(i - lo) < (uint32_t)(hi - lo)) && (((x < find_l) || (x > find_h)) != find_in);
+        if constexpr (FIND == 1) {
+            find_n += hit ? 1u : 0u;
+        } else {
+            if (__builtin_expect(__any(hit), 0)) {
+                if (hit && find_n < find_cap) {
+                    a.find_out[out_off + find_n] = fstart + i;
+                    if (a.find_val) a.find_val[out_off + find_n] = x;
+                    find_n++;
+                }
+            }
+        }
+    };
+
     // one sample of every lane.  GUARD: lanes may be in warm-up or past their frame's end.
     // PART: a partition boundary may fall inside this macro step (decided once per step for the wave)
     auto sample = [&](auto guard_tag, auto part_tag, auto u_tag, int i) __attribute__((always_inline)) {
@@ -1436,6 +1488,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                 red_take(i, wrap32(xd));
             } else if constexpr (HIST) {
                 hist_take(i, wrap32(xd));
+            } else if constexpr (FIND != 0) {
+                find_take(i, wrap32(xd));
             } else {
 #if (FA_K7_X & 4)
             if (u == 0)
@@ -1448,6 +1502,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                 if (i < bs) red_take(i, wrap32(h[u % MO]));
             } else if constexpr (HIST) {
                 if (i < bs) hist_take(i, wrap32(h[u % MO]));  // (as above)
+            } else if constexpr (FIND != 0) {
+                if (i < bs) find_take(i, wrap32(h[u % MO]));  // (as above)
             } else {
             // warm-up sample 16..31 (orders above 16): its value sits in the history
             if (i < bs && i >= kTileW) tile[u * kLaneStride + (lane ^ ((u >> 2) * kTileSwz))] = wrap32(h[u % MO]);
@@ -1732,6 +1788,10 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         }
         if (hist_bel) (void)__hip_atomic_fetch_add(a.hist_below + hist_row, (unsigned long long)hist_bel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (hist_abv) (void)__hip_atomic_fetch_add(a.hist_above + hist_row, (unsigned long long)hist_abv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (FIND == 1) {
+        // one plain store per frame, by the pass that decoded it (the array holds zeros before the first pass)
+        if (find_mine) a.find_out[out_off + (f - a.f0)] = (long long)find_n;
     }
     if constexpr (NCH == 2) {
         if (has_task && task_live) a.assign[task] = ch_assign;  // both subframes decoded

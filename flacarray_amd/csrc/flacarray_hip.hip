@@ -41,6 +41,7 @@
 #include "md5_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "histogram_kernels.hpp"
+#include "find_kernels.hpp"
 #include "scrub_kernels.hpp"
 #include "reindex_kernels.hpp"
 #include "window_kernels.hpp"
@@ -569,6 +570,7 @@ struct ReduceSink {
     const int64_t* sel;
     ReduceOut out;
     const HistOut* hist = nullptr;  // the histogram sink K7H in the reducing sink's place: nbins value bins per row, `width` and `out` unused
+    const FindSink* find = nullptr;  // the search sink K7F in the reducing sink's place: `width`, `nbins` and `out` unused
 };
 
 // device memory for a task table: the index's own (grown on demand) or the cached scratch
@@ -775,7 +777,20 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     if (a.B > kMaxBlock * 16) return FA_ERROR_DECODE_INIT;
     if (red) {
         if (n_slices >= 0) return FA_ERROR_CONVERT_TYPE;
-        if (red->hist) {
+        if (red->find) {
+            // the caller sized its arrays with n_frames frames per row: nothing is written before that is known to hold
+            const FindSink& fs = *red->find;
+            if (fs.n_frames != a.nfr) return FA_ERROR_CONVERT_TYPE;
+            const int64_t cells = (red->sel ? red->n_sel : n_stream) * a.nfr;
+            if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
+            a.find_lo = fs.lo; a.find_hi = fs.hi; a.find_inside = fs.inside ? 1 : 0;
+            if (fs.hit_ids) {
+                a.find_out = fs.pos; a.find_val = fs.val; a.find_ids = fs.hit_ids; a.find_offs = fs.offs;
+            } else {
+                a.find_out = fs.frame_counts; a.find_val = nullptr; a.find_ids = nullptr;
+                a.red_nbins = a.nfr;  // (out_off = row * nfr, as the other folding sinks have row * nbins)
+            }
+        } else if (red->hist) {
             a.hist_counts = red->hist->counts; a.hist_below = red->hist->below; a.hist_above = red->hist->above;
             a.hist_lo = red->hist->lo; a.hist_shift = red->hist->shift;
             a.red_width = 0; a.red_nbins = red->nbins;
@@ -785,7 +800,14 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         a.red_width = red->width; a.red_nbins = red->nbins;
         }
         if (red->sel) a.n_tasks = red->n_sel * a.nfr;  // list mode; the table is built on the device, below
+        if (red->find && red->find->hit_ids) a.n_tasks = red->find->n_hit;  // (the fill pass: the frames with a hit, always a list)
         if (a.n_tasks <= 0 || a.n_tasks > (int64_t)64 * 0x7fffffff) return FA_ERROR_DECODE_SAMPLE_RANGE;
+        if (red->find && !red->find->hit_ids) {
+            // (behind every refusal of the arguments: a refused count call has written nothing)
+            const int64_t cells = (red->sel ? red->n_sel : n_stream) * a.nfr;
+            hipLaunchKernelGGL(find_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, red->find->frame_counts, cells);
+            FA_HIP_TRY(hipGetLastError());
+        }
     }
     const unsigned nblk = (unsigned)((a.n_tasks + 63) / 64);
     const bool f32 = cmp ? (d_offsets != nullptr) : (d_out_f32 != nullptr);
@@ -877,7 +899,18 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         FA_HIP_TRY(hipStreamSynchronize(st));
         tasks_uploaded = true;
     }
-    if (red && red->sel) {
+    if (red && red->find && red->find->hit_ids) {
+        // K7's task table for the frames that hold a hit: task t = cell hit_ids[t], output base offs[cell]
+        const size_t stp = align_up((size_t)a.n_tasks * 8, 256);
+        void* pl = nullptr;
+        if ((rc = task_table_mem(use_index ? idx : nullptr, 5 * stp, &pl))) return rc;
+        int64_t* t5[5];
+        for (int k = 0; k < 5; ++k) t5[k] = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(pl) + k * stp);
+        hipLaunchKernelGGL(find_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, red->find->hit_ids, a.n_tasks,
+                           red->sel ? red->n_sel : n_stream, a.nfr, a.f0, a.first, a.first + a.n_decode, red->sel, n_stream, red->find->offs,
+                           t5[0], t5[1], t5[2], t5[3], t5[4], d_err, (int)FA_ERROR_DECODE_SAMPLE_RANGE);
+        a.task_stream = t5[0]; a.task_frame = t5[1]; a.task_first = t5[2]; a.task_last = t5[3]; a.task_out_off = t5[4];
+    } else if (red && red->sel) {
         // K7's task table for the named streams: task t = (row t / nfr, frame f0 + t % nfr), output slot row * nbins
         const size_t stp = align_up((size_t)a.n_tasks * 8, 256);
         void* pl = nullptr;
@@ -953,7 +986,9 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     const bool verifying_k7 = (verify < 0 ? g_verify.load() : verify != 0);
     const bool beside = verifying_k7 && a.n_tasks >= 16384 && std::getenv("FLACARRAY_HIP_VERIFY_AFTER") == nullptr &&
                         run_verify_beside_begin(st);
-    if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    if (red && red->find && red->find->hit_ids) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    else if (red && red->find) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    else if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     else if (red) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     else if (cmp) {
         if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -967,7 +1002,9 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
     if (h_err[1] & kFlagNeed16) {
-        if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        if (red && red->find && red->find->hit_ids) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (red && red->find) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else if (red) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else if (cmp) {
             if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -976,7 +1013,9 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
     }
     if (h_err[1] & kFlagNeed32) {
-        if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        if (red && red->find && red->find->hit_ids) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (red && red->find) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        else if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else if (red) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
         else if (cmp) {
             if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
@@ -2307,11 +2346,11 @@ static int reduce_store_args(int nch, DecodeIndex* ix, const unsigned char*& d_b
 static int reduce_chunks(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
                          int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t rows, const int64_t* d_sel,
                          int64_t max_temp_bytes, hipStream_t st, int verify,
-                         const std::function<int(const long long*, int64_t, int64_t)>& fold) {
+                         const std::function<int(const long long*, int64_t, int64_t)>& fold, int64_t B_known = 0) {
     const int64_t n = last - first;
     int rc;
-    int64_t B = ix ? ix->B : 0;
-    if (!ix && (rc = reduce_peek_blocksize(d_bytes, n_bytes, d_starts, st, &B))) return rc;
+    int64_t B = ix ? ix->B : B_known;
+    if (B <= 0 && (rc = reduce_peek_blocksize(d_bytes, n_bytes, d_starts, st, &B))) return rc;
     const int64_t sample_bytes = 8;
     const int64_t cap = max_temp_bytes > 0 ? max_temp_bytes : (int64_t)FA_REDUCE_TEMP_BYTES;
     int64_t cw = cap / (rows * sample_bytes) / B * B;
@@ -2472,6 +2511,161 @@ int fa_histogram_indexed(void* index, int64_t first, int64_t last, int64_t n_sel
     if (!ix) return FA_ERROR_DECODE_INIT;
     return histogram_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, n_sel, d_sel_streams, max_temp_bytes, nbins, d_lo, d_shift,
                             d_counts, d_below, d_above, stream, verify);
+}
+
+// ---- search: the positions (and values) of the samples outside per-row limits, without a decoded copy (profiles/find.md) ----
+// Two passes over the same frames.  Count: hits per (row, frame) into the caller's frame_counts.  Fill: after the caller
+// has formed the exclusive prefix sum and listed the cells with a hit, those frames alone are decoded again and their
+// hits written in place.  One-channel streams: the search sink of K7 (K7F).  Two-channel streams: the column chunks of
+// the binned reduction, counted and filled by the find_chunk kernels -- both passes decode every chunk.
+
+// The block size a search plans with: the index's, or the one stream 0's STREAMINFO states (minimum = maximum, the first
+// metadata block).  A header that does not say is an error here: the caller sizes its arrays by the answer.
+static int find_blocksize(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, hipStream_t st, int64_t* B) {
+    if (ix) { *B = ix->B; return ix->B > 0 ? FA_ERROR_NONE : FA_ERROR_DECODE_INIT; }
+    int64_t s0 = -1;
+    FA_HIP_TRY(hipMemcpyAsync(&s0, d_starts, 8, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    if (s0 < 0 || s0 + 12 > n_bytes) return FA_ERROR_DECODE_INIT;
+    unsigned char h[12];
+    FA_HIP_TRY(hipMemcpyAsync(h, d_bytes + s0, 12, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    const int64_t bmin = ((int64_t)h[8] << 8) | h[9], bmax = ((int64_t)h[10] << 8) | h[11];
+    if (std::memcmp(h, "fLaC", 4) != 0 || (h[4] & 0x7f) != 0 || bmin != bmax || bmin <= 0 || bmin > 65535) return FA_ERROR_DECODE_INIT;
+    *B = bmin;
+    return FA_ERROR_NONE;
+}
+
+static int find_plan(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, int64_t stream_size, int64_t first,
+                     int64_t last, int64_t* block_size, int64_t* n_frames, void* stream) {
+    FA_API_LOCK;
+    if (!block_size || !n_frames) return FA_ERROR_CONVERT_TYPE;
+    if (ix) {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess || cur != ix->device) return FA_ERROR_DEVICE;
+        stream_size = ix->stream_size;
+    } else if (!d_bytes || !d_starts) {
+        return FA_ERROR_CONVERT_TYPE;
+    }
+    if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
+    if (first < 0 && last < 0) { first = 0; last = stream_size; }
+    if (first < 0 || last > stream_size || first >= last) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    int rc;
+    int64_t B = 0;
+    if ((rc = find_blocksize(ix, d_bytes, n_bytes, d_starts, reinterpret_cast<hipStream_t>(stream), &B))) return rc;
+    *block_size = B;
+    *n_frames = (last - 1) / B - first / B + 1;
+    return FA_ERROR_NONE;
+}
+
+int fa_find_plan_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, int64_t stream_size, int64_t first, int64_t last,
+                        int64_t* block_size, int64_t* n_frames, void* stream) {
+    return find_plan(nullptr, d_bytes, n_bytes, d_starts, stream_size, first, last, block_size, n_frames, stream);
+}
+
+int fa_find_plan_indexed(void* index, int64_t first, int64_t last, int64_t* block_size, int64_t* n_frames) {
+    DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
+    if (!ix) return FA_ERROR_DECODE_INIT;
+    return find_plan(ix, nullptr, 0, nullptr, 0, first, last, block_size, n_frames, nullptr);
+}
+
+// fill == false: the count pass (d_frame_counts); fill == true: the fill pass (the hit list, the prefix sum, d_pos, d_val)
+static int find_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                       int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel,
+                       int64_t max_temp_bytes, const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t* d_frame_counts,
+                       bool fill, int64_t n_hit, const int64_t* d_hit, const int64_t* d_offs, int64_t* d_pos, int64_t* d_val, void* stream,
+                       int verify) {
+    FA_API_LOCK;
+    int rc;
+    if ((rc = reduce_store_args(nch, ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last))) return rc;
+    if (!d_lo || !d_hi || n_frames < 1) return FA_ERROR_CONVERT_TYPE;
+    if (fill ? (n_hit < 0 || !d_offs || (n_hit > 0 && (!d_hit || !d_pos))) : !d_frame_counts) return FA_ERROR_CONVERT_TYPE;
+    if (d_sel && n_sel <= 0) return n_sel == 0 ? FA_ERROR_NONE : FA_ERROR_CONVERT_TYPE;
+    if (fill && n_hit == 0) return FA_ERROR_NONE;
+    const int64_t rows = d_sel ? n_sel : n_stream;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    FindSink fs;
+    fs.lo = reinterpret_cast<const long long*>(d_lo); fs.hi = reinterpret_cast<const long long*>(d_hi); fs.inside = inside ? 1 : 0;
+    fs.n_frames = n_frames; fs.frame_counts = reinterpret_cast<long long*>(d_frame_counts);
+    fs.n_hit = fill ? n_hit : 0; fs.hit_ids = fill ? reinterpret_cast<const long long*>(d_hit) : nullptr;
+    fs.offs = reinterpret_cast<const long long*>(d_offs); fs.pos = reinterpret_cast<long long*>(d_pos); fs.val = reinterpret_cast<long long*>(d_val);
+    if (nch == 1) {
+        ReduceSink red;
+        red.width = last - first; red.nbins = n_frames; red.n_sel = n_sel; red.sel = d_sel;  // (nbins: the rows' stride in frame_counts)
+        red.out = ReduceOut{nullptr, nullptr, nullptr, nullptr, nullptr, n_frames};
+        red.find = &fs;
+        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last - first, -1, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr,
+                                  0, nullptr, nullptr, nullptr, &red);
+    }
+    int64_t B = 0;
+    if ((rc = find_blocksize(ix, d_bytes, n_bytes, d_starts, st, &B))) return rc;
+    const int64_t f0 = first / B, nfr = (last - 1) / B - f0 + 1;
+    if (n_frames != nfr) return FA_ERROR_CONVERT_TYPE;
+    const int64_t cells = rows * nfr;
+    if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
+    if (!fill) {
+        hipLaunchKernelGGL(find_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, fs.frame_counts, cells);
+        FA_HIP_TRY(hipGetLastError());
+    }
+    return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, rows, d_sel, max_temp_bytes, st, verify,
+                         [&](const long long* tmp, int64_t at, int64_t end) -> int {
+        FindChunk c;
+        c.data = tmp; c.cw = end - at; c.c0 = at; c.nseg = (end - 1) / B - at / B + 1; c.B = B; c.nfr = nfr; c.f0 = f0;
+        c.lo = fs.lo; c.hi = fs.hi; c.inside = fs.inside;
+        if (rows * c.nseg > 0x7fffffff) return FA_ERROR_ALLOC;
+        if (fill) hipLaunchKernelGGL(find_chunk_fill_kernel, dim3((unsigned)(rows * c.nseg)), dim3(64), 0, st, c, fs.offs, fs.pos, fs.val);
+        else hipLaunchKernelGGL(find_chunk_count_kernel, dim3((unsigned)(rows * c.nseg)), dim3(64), 0, st, c, fs.frame_counts);
+        return FA_ERROR_NONE;
+    }, B);
+}
+
+int fa_find_count_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                             int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, const int64_t* d_lo,
+                             const int64_t* d_hi, int inside, int64_t n_frames, int64_t* d_frame_counts, void* stream, int verify) {
+    return find_device(1, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_sel_streams, 0, d_lo, d_hi,
+                       inside, n_frames, d_frame_counts, false, 0, nullptr, nullptr, nullptr, nullptr, stream, verify);
+}
+
+int fa_find_count_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                             int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                             const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t* d_frame_counts, void* stream,
+                             int verify) {
+    return find_device(2, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_sel_streams, max_temp_bytes,
+                       d_lo, d_hi, inside, n_frames, d_frame_counts, false, 0, nullptr, nullptr, nullptr, nullptr, stream, verify);
+}
+
+int fa_find_count_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                          const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t* d_frame_counts, void* stream, int verify) {
+    DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
+    if (!ix) return FA_ERROR_DECODE_INIT;
+    return find_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, n_sel, d_sel_streams, max_temp_bytes, d_lo, d_hi, inside,
+                       n_frames, d_frame_counts, false, 0, nullptr, nullptr, nullptr, nullptr, stream, verify);
+}
+
+int fa_find_fill_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, const int64_t* d_lo,
+                            const int64_t* d_hi, int inside, int64_t n_frames, int64_t n_hit_tasks, const int64_t* d_hit_tasks,
+                            const int64_t* d_frame_offsets, int64_t* d_pos, int64_t* d_val, void* stream, int verify) {
+    return find_device(1, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_sel_streams, 0, d_lo, d_hi,
+                       inside, n_frames, nullptr, true, n_hit_tasks, d_hit_tasks, d_frame_offsets, d_pos, d_val, stream, verify);
+}
+
+int fa_find_fill_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                            const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t n_hit_tasks, const int64_t* d_hit_tasks,
+                            const int64_t* d_frame_offsets, int64_t* d_pos, int64_t* d_val, void* stream, int verify) {
+    return find_device(2, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_sel_streams, max_temp_bytes,
+                       d_lo, d_hi, inside, n_frames, nullptr, true, n_hit_tasks, d_hit_tasks, d_frame_offsets, d_pos, d_val, stream, verify);
+}
+
+int fa_find_fill_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                         const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t n_hit_tasks, const int64_t* d_hit_tasks,
+                         const int64_t* d_frame_offsets, int64_t* d_pos, int64_t* d_val, void* stream, int verify) {
+    DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
+    if (!ix) return FA_ERROR_DECODE_INIT;
+    return find_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, n_sel, d_sel_streams, max_temp_bytes, d_lo, d_hi, inside,
+                       n_frames, nullptr, true, n_hit_tasks, d_hit_tasks, d_frame_offsets, d_pos, d_val, stream, verify);
 }
 
 // ---- damage map and salvage decode (scrub_kernels.hpp) ----

@@ -1511,6 +1511,225 @@ def histogram_flac_device(compressed, starts, nbytes, stream_size, lo, shift, nb
     return counts, below, above
 
 
+_I64_MIN, _I64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def _find_args(rows, lo, hi, inside=False, max_hits=None, floats=False):
+    """The argument checks of the search (ValueError, before anything touches the GPU).  `lo` / `hi`: None (no limit on
+    that side), one number or `rows` of them (array or tensor).  Integer limits (floats=False) must be integers inside
+    int64 -- no bools, no floats; float limits (floats=True) are numbers, +-inf meaning "no limit", NaN refused.
+    `inside` is a bool, `max_hits` None or a non-negative integer.  Returns (lo[rows], hi[rows], inside, max_hits) with
+    int64 or float64 numpy arrays."""
+    torch = _torch()
+    if not isinstance(inside, (bool, np.bool_)):
+        raise ValueError("inside should be True or False")
+    if max_hits is not None and (isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or int(max_hits) < 0):
+        raise ValueError("max_hits should be None or a non-negative integer")
+
+    def column(v, name, missing):
+        if v is None:
+            v = missing
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v)
+        if a.dtype == object:
+            if not all(isinstance(e, (int, np.integer) if not floats else (int, float, np.integer, np.floating)) and
+                       not isinstance(e, (bool, np.bool_)) for e in a.reshape(-1)):
+                raise ValueError(f"{name} should hold {'numbers' if floats else 'integers'}")
+        elif a.dtype.kind == "b":
+            raise ValueError(f"{name} should be {'a number' if floats else 'an integer'}, not a bool")
+        elif a.dtype.kind not in ("iuf" if floats else "iu"):
+            raise ValueError(f"{name} should be {'a number or an array of numbers' if floats else 'an integer or an integer array'}")
+        if a.ndim > 1 or (a.ndim == 1 and a.size != rows):
+            raise ValueError(f"{name} should be one value or {rows} of them, one per row")
+        if floats:
+            a = a.astype(np.float64)
+            if np.isnan(a).any():
+                raise ValueError(f"{name} holds a NaN")
+            return np.array(np.broadcast_to(a, (rows,)))
+        if a.size and (min(int(e) for e in a.reshape(-1)) < _I64_MIN or max(int(e) for e in a.reshape(-1)) > _I64_MAX):
+            raise ValueError(f"{name} holds a value outside int64")
+        return np.array(np.broadcast_to(a.astype(np.int64), (rows,)))  # (a copy: writable and contiguous)
+
+    if floats:
+        return column(lo, "lo", -np.inf), column(hi, "hi", np.inf), bool(inside), None if max_hits is None else int(max_hits)
+    return column(lo, "lo", _I64_MIN), column(hi, "hi", _I64_MAX), bool(inside), None if max_hits is None else int(max_hits)
+
+
+def float_limit_images(restore, lo, hi, qmin, qmax):
+    """The exact integer images of float limits under a monotone restore (pure host function).  `restore(q)` maps an
+    int64 array q (one value per row, inside [qmin, qmax]) to the rows' restored floats and is non-decreasing in q for
+    every row -- offset + coeff * float(q) with a positive coeff is.  Per row, the limits lo / hi (float64; +-inf allowed)
+    become
+        lo_q = the smallest q in [qmin, qmax] with restore(q) >= lo   (qmax + 1 when there is none)
+        hi_q = the largest  q in [qmin, qmax] with restore(q) <= hi   (qmin - 1 when there is none)
+    so that restore(q) < lo  <=>  q < lo_q and restore(q) > hi  <=>  q > hi_q for every q in the range.  The comparisons
+    are made in float64, i.e. exactly.  Found by bisection: one test of the range's end and at most 64 halvings for each
+    limit, every step one call of `restore` for all rows.  Returns two object arrays of Python integers (the sentinels
+    lie outside int64 when the range is int64's)."""
+    lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+    hi = np.asarray(hi, dtype=np.float64).reshape(-1)
+    rows = lo.size
+    qmin, qmax = int(qmin), int(qmax)
+
+    def first_true(pred):
+        # the smallest q with pred(q), pred being false ... false true ... true over the range; qmax + 1 when never true
+        a = np.full(rows, qmin, dtype=object)
+        b = np.full(rows, qmax + 1, dtype=object)
+        if rows == 0:
+            return b
+        top = pred(np.full(rows, qmax, dtype=np.int64))
+        b[top] = qmax
+        a[~top] = qmax + 1
+        for _ in range(64):
+            if not (a < b).any():
+                break
+            mid = (a + b) // 2  # (< b <= qmax wherever a < b; rows that are done get a value in range all the same)
+            m = np.clip(mid, qmin, qmax).astype(np.int64)
+            t = pred(m)
+            open_ = a < b
+            b = np.where(open_ & t, mid, b)
+            a = np.where(open_ & ~t, mid + 1, a)
+        assert not (a < b).any()
+        return b
+
+    lo_q = first_true(lambda q: np.asarray(restore(q), dtype=np.float64) >= lo)
+    hi_q = first_true(lambda q: np.asarray(restore(q), dtype=np.float64) > hi) - 1
+    return lo_q, hi_q
+
+
+def float_limits_to_int(restore, lo, hi, qmin, qmax):
+    """float_limit_images as the int64 limits the search takes: a row with no q at or above lo, or none at or below hi,
+    has every sample outside its limits and gets (INT64_MAX, INT64_MIN)-style limits with lo > hi placed so that every
+    integer of the range is outside them; every other row gets its images, clipped into int64 (an image one past the
+    range is as good as the range's end: no sample lies there)."""
+    lo_q, hi_q = float_limit_images(restore, lo, hi, qmin, qmax)
+    lo_i = np.empty(lo_q.size, dtype=np.int64)
+    hi_i = np.empty(lo_q.size, dtype=np.int64)
+    for r in range(lo_q.size):
+        if lo_q[r] > qmax or hi_q[r] < qmin:  # everything is below lo, or everything is above hi
+            lo_i[r], hi_i[r] = qmax, qmin  # q < qmax or q > qmin: every q of the range (qmin < qmax)
+        else:
+            lo_i[r], hi_i[r] = lo_q[r], hi_q[r]
+    return lo_i, hi_i
+
+
+def _find_passes(dev, rows, plan, count_call, fill_call, counts_only, values, max_hits):
+    """The two passes of the search on device tensors.  plan() -> (errcode, block size, frames per row); count_call(nfr,
+    frame_counts) and fill_call(nfr, n_hit, hit, offs, pos, val) -> errcode.  Between them: the exclusive prefix sum of the
+    per-frame counts, the cells that hold a hit, and the one host read of the total."""
+    torch = _torch()
+    err, _, nfr = plan()
+    if err != 0:
+        raise RuntimeError(f"Decoding failed, return code = {err} (the search needs streams of one stated block size)")
+    cells = rows * nfr
+    frame_counts = torch.empty((cells,), dtype=torch.int64, device=dev)
+    err = count_call(nfr, frame_counts)
+    if err != 0:
+        raise RuntimeError(f"Decoding failed, return code = {err}")
+    counts = frame_counts.view(rows, nfr).sum(dim=1)
+    if counts_only:
+        return counts, None, None
+    offs = torch.empty((cells + 1,), dtype=torch.int64, device=dev)
+    offs[:1] = 0
+    torch.cumsum(frame_counts, dim=0, out=offs[1:])
+    total = int(offs[-1].item())
+    if max_hits is not None and total > max_hits:
+        raise ValueError(f"the search found {total} hits, more than max_hits = {max_hits}")
+    pos = torch.empty((total,), dtype=torch.int64, device=dev)
+    val = torch.empty((total,), dtype=torch.int64, device=dev) if values else None
+    if total:
+        hit = torch.nonzero(frame_counts).reshape(-1).contiguous()
+        err = fill_call(nfr, int(hit.numel()), hit, offs, pos, val)
+        if err != 0:
+            raise RuntimeError(f"Decoding failed, return code = {err}")
+    return counts, pos, val
+
+
+def _find_store_checks(compressed, starts, nbytes, name):
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64:
+        raise ValueError("starts and nbytes should be of type int64")
+    if starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes must have the same shape")
+    n_stream = int(np.prod(starts.shape))
+    if n_stream <= 0:
+        raise ValueError("starts needs at least one stream")
+    return n_stream
+
+
+def find_flac_device(compressed, starts, nbytes, stream_size, lo=None, hi=None, first_sample=0, last_sample=None, streams=None, inside=False,
+                     values=True, max_hits=None, is_int64=False, verify=None, max_temp_bytes=None, _counts_only=False):
+    """Where are the samples outside per-row limits -- the positions, and values, of the hits in what device-resident
+    streams decode to, without a decoded copy (fa_find_count_* / fa_find_fill_*).  Sample x of row r at position t in
+    [first_sample, last_sample) is a hit iff (x < lo[r] or x > hi[r]) != inside: by default the samples outside the closed
+    interval, with inside=True those in it (lo == hi == v finds a sentinel value).  `lo` / `hi` are int64: a Python
+    integer or `rows` of them, None meaning no limit on that side; lo > hi is legal (everything hits, or with inside=True
+    nothing).  Rows are all streams, or the streams that `streams` names, in that order.
+
+    Returns (counts [rows], positions [total], values [total] or None when values=False): int64 device tensors over the
+    decoded INTEGERS (for a float store the quantised ones).  The hits are listed exactly once, sorted by (row,
+    position): row r owns positions[offsets[r]:offsets[r + 1]], offsets being the exclusive prefix sum of counts.  This
+    equals np.nonzero of the same predicate on the decoded integers.  No atomics place the hits, so the result does not
+    depend on the order of arrival.  More than `max_hits` hits raise ValueError, which names the total, before the second
+    pass runs or the position buffers exist.
+
+    Two passes: K7F counts the hits per (row, frame) inside the decoder, torch forms the prefix sum and lists the frames
+    that hold a hit, and K7F decodes those frames alone again and writes their hits in place.  Two-channel streams
+    (is_int64) go through decoded column chunks of whole frames under `max_temp_bytes` (default 256 MiB) in BOTH passes,
+    as reduce_flac_device's do: the documented slow route (profiles/find.md).  The streams must state one block size in
+    their STREAMINFO.  `verify` is the decoder's frame CRC-16 check; argument errors raise ValueError before any GPU work,
+    decode failures the decoder's RuntimeError."""
+    torch = _torch()
+    n_stream = _find_store_checks(compressed, starts, nbytes, "find_flac_device")
+    first, last, _, _, idx = _reduce_args(n_stream, stream_size, None, first_sample, last_sample, streams)
+    rows = n_stream if idx is None else int(idx.size)
+    lo_h, hi_h, inside, max_hits = _find_args(rows, lo, hi, inside, max_hits)
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("find_flac_device needs compressed, starts and nbytes on the same GPU")
+    if rows == 0:
+        z = torch.zeros((0,), dtype=torch.int64, device=dev)
+        return z, (None if _counts_only else z.clone()), (z.clone() if values and not _counts_only else None)
+    sel = None if idx is None else torch.from_numpy(idx).to(dev)
+    d_lo, d_hi = torch.from_numpy(lo_h).to(dev), torch.from_numpy(hi_h).to(dev)
+    cap = 0 if max_temp_bytes is None else int(max_temp_bytes)
+    L = _lib.lib()
+    store = (_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last, rows, _dp(sel))
+    mid = (cap,) if is_int64 else ()
+
+    def plan():
+        B, nfr = ctypes.c_int64(0), ctypes.c_int64(0)
+        e = L.fa_find_plan_device(_dp(compressed), compressed.numel(), _dp(starts), stream_size, first, last, ctypes.byref(B), ctypes.byref(nfr),
+                                  _stream_ptr())
+        return e, B.value, nfr.value
+
+    def count_call(nfr, fc):
+        f = L.fa_find_count_i64_device if is_int64 else L.fa_find_count_i32_device
+        return f(*store, *mid, _dp(d_lo), _dp(d_hi), int(inside), nfr, _dp(fc), _stream_ptr(), _verify_arg(verify))
+
+    def fill_call(nfr, n_hit, hit, offs, pos, val):
+        f = L.fa_find_fill_i64_device if is_int64 else L.fa_find_fill_i32_device
+        return f(*store, *mid, _dp(d_lo), _dp(d_hi), int(inside), nfr, n_hit, _dp(hit), _dp(offs), _dp(pos), _dp(val), _stream_ptr(),
+                 _verify_arg(verify))
+
+    with _on_device(dev):
+        return _find_passes(dev, rows, plan, count_call, fill_call, _counts_only, values, max_hits)
+
+
+def find_counts_flac_device(compressed, starts, nbytes, stream_size, lo=None, hi=None, first_sample=0, last_sample=None, streams=None,
+                            inside=False, is_int64=False, verify=None, max_temp_bytes=None):
+    """The first pass of find_flac_device alone: counts [rows], an int64 device tensor -- how many samples of each row
+    are hits.  Measured (profiles/find.md): 6.3-6.5 ms at 4096 x 2^20 int32 (the bare
+    decode: 6.35 ms; reduce with one bin: 7.2), 53 ms at 1024 x 2^20 int64 (a chunked decode, as reduce's)."""
+    return find_flac_device(compressed, starts, nbytes, stream_size, lo, hi, first_sample, last_sample, streams, inside, False, None, is_int64,
+                            verify, max_temp_bytes, _counts_only=True)[0]
+
+
 class DeviceDecodeIndex:
     """Decode index of one HBM-resident store (fa_decode_index_create): the stream headers are parsed and the byte
     offset of every frame is tabulated ONCE; `decode` / `decode_slices` then cost one kernel launch each.  Holds
@@ -1620,6 +1839,43 @@ class DeviceDecodeIndex:
         if errcode != 0:
             raise RuntimeError(f"Decoding failed, return code = {errcode}")
         return counts, below, above
+
+    def find(self, lo=None, hi=None, first_sample=0, last_sample=None, streams=None, inside=False, values=True, max_hits=None, verify=None,
+             max_temp_bytes=None, _counts_only=False):
+        """find_flac_device on the indexed store (fa_find_count_indexed / fa_find_fill_indexed): nothing is parsed again.
+        Returns (counts [rows], positions [total], values [total] or None), int64 tensors."""
+        torch = _torch()
+        first, last, _, _, idx = _reduce_args(self.n_stream, self.stream_size, None, first_sample, last_sample, streams)
+        rows = self.n_stream if idx is None else int(idx.size)
+        lo_h, hi_h, inside, max_hits = _find_args(rows, lo, hi, inside, max_hits)
+        dev = self.device
+        if rows == 0:
+            z = torch.zeros((0,), dtype=torch.int64, device=dev)
+            return z, (None if _counts_only else z.clone()), (z.clone() if values and not _counts_only else None)
+        sel = None if idx is None else torch.from_numpy(idx).to(dev)
+        d_lo, d_hi = torch.from_numpy(lo_h).to(dev), torch.from_numpy(hi_h).to(dev)
+        cap = 0 if max_temp_bytes is None else int(max_temp_bytes)
+        L = self._L
+
+        def plan():
+            B, nfr = ctypes.c_int64(0), ctypes.c_int64(0)
+            e = L.fa_find_plan_indexed(self._h, first, last, ctypes.byref(B), ctypes.byref(nfr))
+            return e, B.value, nfr.value
+
+        def count_call(nfr, fc):
+            return L.fa_find_count_indexed(self._h, first, last, rows, _dp(sel), cap, _dp(d_lo), _dp(d_hi), int(inside), nfr, _dp(fc), _stream_ptr(),
+                                           _verify_arg(verify))
+
+        def fill_call(nfr, n_hit, hit, offs, pos, val):
+            return L.fa_find_fill_indexed(self._h, first, last, rows, _dp(sel), cap, _dp(d_lo), _dp(d_hi), int(inside), nfr, n_hit, _dp(hit), _dp(offs),
+                                          _dp(pos), _dp(val), _stream_ptr(), _verify_arg(verify))
+
+        with _on_device(dev):
+            return _find_passes(dev, rows, plan, count_call, fill_call, _counts_only, values, max_hits)
+
+    def find_counts(self, lo=None, hi=None, first_sample=0, last_sample=None, streams=None, inside=False, verify=None, max_temp_bytes=None):
+        """The first pass of `find` alone: counts [rows], an int64 tensor."""
+        return self.find(lo, hi, first_sample, last_sample, streams, inside, False, None, verify, max_temp_bytes, _counts_only=True)[0]
 
     def decode_slices(self, slice_stream, slice_first, slice_count, offsets=None, gains=None, verify=None, to_host=False):
         """Batched random access (see decode_slices_device): returns (flat tensor, int64 numpy array of offsets);

@@ -434,6 +434,49 @@ int fa_histogram_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const
 int fa_histogram_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes, int64_t nbins,
                          const int64_t* d_lo, const int32_t* d_shift, int64_t* d_counts, int64_t* d_below, int64_t* d_above, void* stream, int verify);
 
+/* ---- search: where are the samples outside per-row limits, without a decoded copy (profiles/find.md).  Store, range, rows
+ * (d_sel_streams / n_sel), max_temp_bytes, `verify`, errors and stream ordering are fa_reduce_*'s.  d_lo / d_hi are int64
+ * DEVICE arrays of `rows` elements; a sample x of row r is a hit iff (x < d_lo[r] || x > d_hi[r]) != (inside != 0) -- inside
+ * == 0: outside the closed interval.  The search runs in two calls, with the caller's prefix sum between them:
+ *   fa_find_plan_*   block_size and n_frames = the frames per row that meet [first, last) (host outputs).  The block size is
+ *                    the index's, or the one stream 0's STREAMINFO states; a header that states none (minimum != maximum)
+ *                    fails with FA_ERROR_DECODE_INIT.
+ *   fa_find_count_*  d_frame_counts[row * n_frames + k] = hits in frame first / block_size + k of row `row` (int64 device
+ *                    array of rows * n_frames elements, set to zero by the call on `stream` first).  n_frames must be the
+ *                    number of frames the decoder works with: otherwise FA_ERROR_CONVERT_TYPE, and nothing is written.
+ *   fa_find_fill_*   d_frame_offsets: rows * n_frames + 1 int64, the exclusive prefix sum of the counts (the last entry
+ *                    the total); d_hit_tasks: the n_hit_tasks cells with a non-zero count, ascending.  Only those frames are
+ *                    decoded again.  The k-th hit of cell c goes to d_pos[d_frame_offsets[c] + k] (the sample's index in its
+ *                    stream) and, when d_val is not null, d_val[...] (its value, int64): hits come out sorted by (row,
+ *                    position).  No cell writes more than its count.  Same limits, `inside`, range and rows as the count
+ *                    call.  d_pos / d_val are complete only after the call's own synchronisation, i.e. when it returns.
+ * No atomics place the hits: the result does not depend on the order of arrival.  One-channel streams are searched inside
+ * the decoder (K7F); two-channel streams go through the decoded column chunks of fa_reduce_i64_device in BOTH calls.  What
+ * is tested is what any FLAC decoder produces -- for float stores the quantised integers. ---- */
+int fa_find_plan_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, int64_t stream_size, int64_t first, int64_t last,
+                        int64_t* block_size, int64_t* n_frames, void* stream);
+int fa_find_plan_indexed(void* index, int64_t first, int64_t last, int64_t* block_size, int64_t* n_frames);
+int fa_find_count_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                             int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, const int64_t* d_lo,
+                             const int64_t* d_hi, int inside, int64_t n_frames, int64_t* d_frame_counts, void* stream, int verify);
+int fa_find_count_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                             int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                             const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t* d_frame_counts, void* stream,
+                             int verify);
+int fa_find_count_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                          const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t* d_frame_counts, void* stream, int verify);
+int fa_find_fill_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, const int64_t* d_lo,
+                            const int64_t* d_hi, int inside, int64_t n_frames, int64_t n_hit_tasks, const int64_t* d_hit_tasks,
+                            const int64_t* d_frame_offsets, int64_t* d_pos, int64_t* d_val, void* stream, int verify);
+int fa_find_fill_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                            int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                            const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t n_hit_tasks, const int64_t* d_hit_tasks,
+                            const int64_t* d_frame_offsets, int64_t* d_pos, int64_t* d_val, void* stream, int verify);
+int fa_find_fill_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
+                         const int64_t* d_lo, const int64_t* d_hi, int inside, int64_t n_frames, int64_t n_hit_tasks, const int64_t* d_hit_tasks,
+                         const int64_t* d_frame_offsets, int64_t* d_pos, int64_t* d_val, void* stream, int verify);
+
 /* ---- damage map and decode through errors.  The decode, compare, reduce and MD5 entry points give up a whole call for one
  * bad frame; these answer per (stream, frame), from nothing but the store, and decode what is intact.
  * fa_frame_status_device writes d_status[n_stream][nf] (device, one byte each), nf = ceil(stream_size / block_size):

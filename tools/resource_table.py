@@ -1,6 +1,6 @@
 """Per-kernel resource usage from a compile log with -Rpass-analysis=kernel-resource-usage, as a markdown table or as a
 comparison of two logs.  Kernels are keyed by their demangled name -- template arguments spelled out, defaulted trailing
-`false` arguments dropped -- so that a template parameter added with a default does not turn every row into a new one.
+`false` / `0` arguments dropped -- so that a template parameter added with a default does not turn every row into a new one.
 
     hipcc ... -Rpass-analysis=kernel-resource-usage --cuda-device-only -c -o /dev/null unit.hip 2> log.txt
     python tools/resource_table.py log.txt [--only decode_frames_kernel]
@@ -20,14 +20,14 @@ def demangle(names):
 
 
 def key_of(demangled):
-    """`void fa::k<8, -1, false, 1, false, true>(args)` -> `k<8, -1, false, 1, false, true>`, trailing `, false` dropped."""
+    """`void fa::k<8, -1, false, 1, false, true>(args)` -> `k<8, -1, false, 1, false, true>`, trailing `, false` and `, 0` dropped."""
     m = re.match(r"(?:void )?(?:fa::)?([\w:]+)(<.*>)?\(", demangled)
     if not m:
         return demangled
     name, targs = m.group(1), m.group(2) or ""
     if targs:
         parts = [p.strip() for p in targs[1:-1].split(",")]
-        while len(parts) > 1 and parts[-1] == "false":
+        while len(parts) > 1 and parts[-1] in ("false", "0"):  # (defaults of added parameters: `bool X = false`, `int X = 0`)
             parts.pop()
         targs = "<" + ", ".join(parts) + ">"
     return name + targs
