@@ -563,15 +563,71 @@ struct DecodeIndex {
     int device = -1;
 };
 
-// The reducing sink of K7 (fa_reduce_*, one channel): bins of `width` samples over the decoded range, the rows of the
-// result being all streams (sel == nullptr) or the n_sel streams a device array names; the bin arrays hold the identities.
-struct ReduceSink {
-    int64_t width, nbins, n_sel;
+// A folding sink of K7 (one channel: fa_reduce_*, fa_histogram_*, fa_find_*): what the decoded samples of the range are
+// folded into where an output would stand.  The rows of the result are all streams (sel == nullptr) or the n_sel streams
+// a device array names; the caller's arrays hold the identities, except the find count's, which the driver zeroes.
+struct ReduceBins { int64_t width; ReduceOut out; };
+struct FoldSink {
+    enum Kind { kReduce, kHist, kFindCount, kFindFill } kind;
+    int64_t n_sel;
     const int64_t* sel;
-    ReduceOut out;
-    const HistOut* hist = nullptr;  // the histogram sink K7H in the reducing sink's place: nbins value bins per row, `width` and `out` unused
-    const FindSink* find = nullptr;  // the search sink K7F in the reducing sink's place: `width`, `nbins` and `out` unused
+    union {
+        ReduceBins red;  // kReduce: red.out.nbins bins of `width` samples per row
+        HistOut hist;    // kHist (K7H): hist.nbins value bins per row
+        FindSink find;   // kFindCount, kFindFill (K7F): frame_counts, or hit_ids / offs / pos / val
+    };
 };
+
+// One decode: the store, the selection, one destination.  Each caller sets the fields it uses.
+struct DecodeRequest {
+    // the store: its three arrays and sizes, or an index of it (the arrays are then not looked at)
+    const unsigned char* bytes = nullptr;
+    const int64_t *starts = nullptr, *nbytes = nullptr;
+    int64_t n_bytes = 0, n_stream = 0, stream_size = 0;
+    DecodeIndex* idx = nullptr;
+    int nch = 1;
+    // the selection: [first, first + n_decode) of every stream (grid mode), or n_slices >= 0 slices in four host arrays
+    int64_t first = 0, n_decode = 0, n_slices = -1;
+    const int64_t *slice_stream = nullptr, *slice_first = nullptr, *slice_count = nullptr, *out_offset = nullptr;
+    hipStream_t st = nullptr;
+    int verify = -1;
+    // the destination.  Device output: int32 / float32 arrays with nch == 1, int64 / float64 arrays with nch == 2 ...
+    void *out_int = nullptr, *out_float = nullptr;
+    const void *offsets = nullptr, *gains = nullptr;
+    // ... and, with it, a host landing for a small one-channel read (*copied: the samples are at h_copy already)
+    void* h_copy = nullptr;
+    size_t h_copy_bytes = 0;
+    bool* copied = nullptr;
+    // the compare sink (first_mismatch != null): whole streams through K7 in grid mode, the caller's samples at cmp in
+    // place of an output (floating point when offsets / gains are given); a frame that is rejected or cannot be located
+    // marks its stream instead of setting the error word, so only errors of the stream headers are returned
+    const void* cmp = nullptr;
+    int64_t* first_mismatch = nullptr;
+    // a folding sink (one channel): the range in grid mode over all streams, or in list mode over the streams named --
+    // the sink's arrays stand where the output would be, and errors are the plain decode's
+    const FoldSink* fold = nullptr;
+
+    DecodeRequest& store(const unsigned char* b, int64_t nb, const int64_t* s, const int64_t* n, int64_t ns, int64_t size) {
+        bytes = b; n_bytes = nb; starts = s; nbytes = n; n_stream = ns; stream_size = size; return *this;
+    }
+    DecodeRequest& slices(int64_t n, const int64_t* s, const int64_t* f, const int64_t* c, const int64_t* o) {
+        n_slices = n; slice_stream = s; slice_first = f; slice_count = c; out_offset = o; return *this;
+    }
+    DecodeRequest& output(void* oi, void* of, const void* off, const void* g) { out_int = oi; out_float = of; offsets = off; gains = g; return *this; }
+};
+
+// what the fa_decode_* calls ask of their output arguments: exactly one array, a floating-point one with offsets and gains
+int check_output_args(const void* out_int, const void* out_float, const void* offsets, const void* gains) {
+    if ((out_int == nullptr) == (out_float == nullptr)) return FA_ERROR_CONVERT_TYPE;
+    if (out_float && (!offsets || !gains)) return FA_ERROR_CONVERT_TYPE;
+    return FA_ERROR_NONE;
+}
+
+// an index is used on the device that holds it (its tables, the store and the call's lock are that device's)
+int index_on_device(const DecodeIndex* ix) {
+    int cur = -1;
+    return (hipGetDevice(&cur) != hipSuccess || cur != ix->device) ? FA_ERROR_DEVICE : FA_ERROR_NONE;
+}
 
 // device memory for a task table: the index's own (grown on demand) or the cached scratch
 int task_table_mem(DecodeIndex* idx, size_t bytes, void** out) {
@@ -586,70 +642,68 @@ int task_table_mem(DecodeIndex* idx, size_t bytes, void** out) {
     return FA_ERROR_NONE;
 }
 
-// idx == nullptr: parse + index into the cached scratch, then decode (one-off calls).
-// idx != nullptr, build_only: parse + index into buffers owned by *idx, no decode.
-// idx != nullptr, !build_only: decode with the index (d_bytes / d_starts / d_nbytes are not looked at).
-int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
-                       int64_t n_stream, int64_t stream_size, int64_t first_decode, int64_t n_decode, int64_t n_slices,
-                       const int64_t* slice_stream, const int64_t* slice_first, const int64_t* slice_count,
-                       const int64_t* out_offset, int32_t* d_out_i32, float* d_out_f32, const float* d_offsets,
-                       const float* d_gains, hipStream_t st, int nch = 1, int64_t* d_out_i64 = nullptr, double* d_out_f64 = nullptr,
-                       const double* d_offsets64 = nullptr, const double* d_gains64 = nullptr, DecodeIndex* idx = nullptr,
-                       bool build_only = false, int verify = -1, void* h_copy = nullptr, size_t h_copy_bytes = 0,
-                       bool* h_copied = nullptr, const void* d_cmp = nullptr, int64_t* d_first_mismatch = nullptr,
-                       const ReduceSink* red = nullptr) {
-    // compare sink (d_first_mismatch != null): whole streams through K7 in grid mode, the caller's samples at d_cmp in place
-    // of an output (float32 / float64 when offsets / gains are given); a frame that is rejected or cannot be located marks
-    // its stream instead of setting the error word, so only errors of the stream headers are returned
-    const bool cmp = (d_first_mismatch != nullptr);
-#ifdef FA_DEV_MINIMAL
-    if (cmp || red) return FA_ERROR_CONVERT_TYPE;
-#endif
-    if (cmp) verify = 0;
-    // reducing sink (red != null, one channel): the range in grid mode over all streams, or in list mode over the streams
-    // named -- the bin arrays stand where the output would be, and errors are the plain decode's
-    if (red && (nch != 1 || cmp)) return FA_ERROR_CONVERT_TYPE;
+// K7's task table in memory: five columns [stream | frame | first | last | out offset] of n_tasks entries each, every
+// column 256-byte aligned.  task_table_place: memory for a.n_tasks tasks (task_table_mem), the columns, `a` pointed at them.
+size_t task_table_bytes(int64_t n_tasks) { return 5 * align_up((size_t)n_tasks * 8, 256); }
+int task_table_place(DecodeIndex* idx, DecodeArgs& a, int64_t* col[5]) {
+    const size_t bytes = task_table_bytes(a.n_tasks);
+    void* p = nullptr;
+    int rc = task_table_mem(idx, bytes, &p);
+    if (rc) return rc;
+    for (int k = 0; k < 5; ++k) col[k] = reinterpret_cast<int64_t*>(static_cast<char*>(p) + k * (bytes / 5));
+    a.task_stream = col[0]; a.task_frame = col[1]; a.task_first = col[2]; a.task_last = col[3]; a.task_out_off = col[4];
+    return FA_ERROR_NONE;
+}
+
+// a task table that so far rides in K7L's kernel arguments only: its host image, and where it goes when K7 or the CRC-16
+// check, which read the table from memory, are needed after all
+struct HeldTasks {
+    std::vector<int64_t> host;
+    void* dev = nullptr;
+    bool uploaded = false;
+    int upload(hipStream_t st) {
+        FA_HIP_TRY(hipMemcpyAsync(dev, host.data(), host.size() * 8, hipMemcpyHostToDevice, st));
+        FA_HIP_TRY(hipStreamSynchronize(st));
+        uploaded = true;
+        return FA_ERROR_NONE;
+    }
+};
+
+// the find count's zero-fill (issued behind every refusal of the arguments: a refused count call has written nothing)
+int find_zero_counts(const FindSink& fs, int64_t cells, hipStream_t st) {
+    hipLaunchKernelGGL(find_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, fs.frame_counts, cells);
+    FA_HIP_TRY(hipGetLastError());
+    return FA_ERROR_NONE;
+}
+
+// K6 as one step: the stream metadata and the byte offset of every frame of a store, into *t.
+// own == false: the tables live in the cached scratch (slots 1 and 2) and are the running call's; errors the walk finds
+// arrive with K7's status words.  own == true: they are hipMalloc'ed (the caller frees t->meta and t->ftab, also after an
+// error) and the error word is read back here.  A store that is not 16-byte aligned is copied to slot 7 first (the
+// kernels issue 16-byte loads relative to the blob base): t->bytes is what the tables refer to.
+int build_decode_tables(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                        int64_t stream_size, int nch, hipStream_t st, bool own, DecodeIndex* t) {
     int rc = FA_ERROR_NONE;
     int h_err[4] = {0, 0, 0, 0};
-    bool err_cleared = true;  // (the one-off path clears them before K6)
-    StreamMeta* d_meta = nullptr;
-    int64_t* d_ftab = nullptr;
-    int* d_err = nullptr;
-    int32_t B = 0;
-    int64_t nf = 0;
-    const bool use_index = (idx != nullptr) && !build_only;
-    if (use_index) {
-        d_bytes = idx->bytes; n_bytes = idx->n_bytes; n_stream = idx->n_stream; stream_size = idx->stream_size;
-        d_meta = idx->meta; d_ftab = idx->ftab; d_err = idx->err; B = idx->B; nf = idx->nf;
-        if (idx->nch != nch) return FA_ERROR_DECODE_INIT;
-        err_cleared = false;
-        prof_begin(4, st);
-        // (the status words are cleared where they are first needed: a small read that lands in pinned host memory
-        // never looks at them, and a memset is a launch of its own)
-    } else {
-    // the decode kernel issues 16-byte loads relative to the blob base: realign if necessary
-    if (build_only && (reinterpret_cast<uintptr_t>(d_bytes) & 15)) return FA_ERROR_DECODE_INIT;  // (an index refers to the caller's bytes)
     if (reinterpret_cast<uintptr_t>(d_bytes) & 15) {
         void* al = nullptr;
-        int rc0 = get_scratch(7, (size_t)n_bytes + 256, &al);
-        if (rc0) return rc0;
+        if ((rc = get_scratch(7, (size_t)n_bytes + 256, &al))) return rc;
         FA_HIP_TRY(hipMemcpyAsync(al, d_bytes, (size_t)n_bytes, hipMemcpyDeviceToDevice, st));
         d_bytes = reinterpret_cast<const unsigned char*>(al);
     }
-    // ---- K6: parse stream headers ----
+    // ---- parse stream headers ----
     prof_begin(4, st);
     void* p = nullptr;
     const size_t meta_bytes = align_up((size_t)n_stream * sizeof(StreamMeta), 256);
-    if (build_only) {
+    if (own) {
         FA_HIP_TRY(hipMalloc(&p, meta_bytes + 256 + (size_t)n_stream * 4));
-        idx->meta = reinterpret_cast<StreamMeta*>(p);  // (fa_decode_index_destroy frees what is set, also after an error)
+        t->meta = reinterpret_cast<StreamMeta*>(p);
     } else {
-        rc = get_scratch(1, meta_bytes + 256 + (size_t)n_stream * 4, &p);
-        if (rc) return rc;
+        if ((rc = get_scratch(1, meta_bytes + 256 + (size_t)n_stream * 4, &p))) return rc;
     }
-    d_meta = reinterpret_cast<StreamMeta*>(p);
+    StreamMeta* d_meta = reinterpret_cast<StreamMeta*>(p);
     // [0]=err [1]=variant flags [2]=streams without a seek table [3]=scan passes of the longest of them
-    d_err = reinterpret_cast<int*>(reinterpret_cast<char*>(p) + meta_bytes);
+    int* d_err = reinterpret_cast<int*>(reinterpret_cast<char*>(p) + meta_bytes);
     int* d_sflag = d_err + 64;  // per stream: 1 = sync scan ambiguous, walk serially
     FA_HIP_TRY(hipMemsetAsync(d_err, 0, 32, st));  // ([4]: the latency kernel's "repeat with K7" flag)
     hipLaunchKernelGGL(parse_streams_kernel, dim3((unsigned)((n_stream + 255) / 256)), dim3(256), 0, st, d_bytes, d_starts,
@@ -659,22 +713,21 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
     if (h_err[0]) return h_err[0];
-    B = m0.B;
+    const int32_t B = m0.B;
     if (m0.channels != nch) return FA_ERROR_DECODE_INIT;  // an int32 stream read as int64 or the reverse
     if (B <= 0 || B > 65535) return FA_ERROR_DECODE_INIT;
     if (B > kMaxBlock * 16) return FA_ERROR_DECODE_INIT;
-    nf = (stream_size + B - 1) / B;
+    const int64_t nf = (stream_size + B - 1) / B;
 
     // ---- frame table ----
     void* pt = nullptr;
-    if (build_only) {
+    if (own) {
         FA_HIP_TRY(hipMalloc(&pt, (size_t)n_stream * (size_t)nf * 8 + 256));
-        idx->ftab = reinterpret_cast<int64_t*>(pt);
+        t->ftab = reinterpret_cast<int64_t*>(pt);
     } else {
-        rc = get_scratch(2, (size_t)n_stream * (size_t)nf * 8 + 256, &pt);
-        if (rc) return rc;
+        if ((rc = get_scratch(2, (size_t)n_stream * (size_t)nf * 8 + 256, &pt))) return rc;
     }
-    d_ftab = reinterpret_cast<int64_t*>(pt);
+    int64_t* d_ftab = reinterpret_cast<int64_t*>(pt);
     const int64_t nt = n_stream * nf;
     hipLaunchKernelGGL(build_frame_table_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_bytes, d_meta, n_stream,
                        nf, B, nch, d_ftab, d_err);
@@ -691,237 +744,273 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
         hipLaunchKernelGGL(walk_frames_kernel, dim3((unsigned)((n_stream + 63) / 64)), dim3(64), 0, st, d_bytes, n_bytes, d_meta,
                            n_stream, nf, B, stream_size, d_ftab, scan ? d_sflag : (const int*)nullptr, d_err);
     }
-    if (build_only) {
+    if (own) {
         FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(hipStreamSynchronize(st));
         FA_HIP_TRY(hipGetLastError());
         if (h_err[0]) return h_err[0];
-        idx->bytes = d_bytes; idx->n_bytes = n_bytes; idx->n_stream = n_stream; idx->stream_size = stream_size; idx->nf = nf;
-        idx->B = B; idx->nch = nch; idx->err = d_err;
-        return FA_ERROR_NONE;
     }
-    }  // (!use_index)
+    t->bytes = d_bytes; t->n_bytes = n_bytes; t->n_stream = n_stream; t->stream_size = stream_size; t->nf = nf;
+    t->B = B; t->nch = nch; t->meta = d_meta; t->ftab = d_ftab; t->err = d_err;
+    return FA_ERROR_NONE;
+}
 
-    // ---- K7 ----
+// K7's launch, written once: the sink picks the specialisation of the <MO, MO_DONE> history pass.  f32: floating-point
+// output (or, compare sink, floating-point samples to compare with).
+template <int MO, int MO_DONE>
+void launch_k7(const DecodeArgs& a, int nch, bool cmp, bool f32, const FoldSink* fold, hipStream_t st) {
+    const dim3 grid((unsigned)((a.n_tasks + 63) / 64)), block(64);
+#define FA_K7(...) hipLaunchKernelGGL((decode_frames_kernel<MO, MO_DONE, __VA_ARGS__>), grid, block, 0, st, a, a.err + 1)
+#ifdef FA_DEV_MINIMAL
+    (void)nch; (void)cmp; (void)f32; (void)fold;
+    FA_K7(false, 1);
+#else
+    // (two channels, compare: the same decode, but a frame it rejects marks its stream -- K8C cannot tell a frame abandoned half way)
+    if (nch == 2) { if (cmp) FA_K7(false, 2, true); else FA_K7(false, 2); }
+    else if (fold && fold->kind == FoldSink::kFindFill) FA_K7(false, 1, false, false, false, 2);
+    else if (fold && fold->kind == FoldSink::kFindCount) FA_K7(false, 1, false, false, false, 1);
+    else if (fold && fold->kind == FoldSink::kHist) FA_K7(false, 1, false, false, true);
+    else if (fold) FA_K7(false, 1, false, true);
+    else if (cmp) { if (f32) FA_K7(true, 1, true); else FA_K7(false, 1, true); }
+    else if (f32) FA_K7(true, 1);
+    else FA_K7(false, 1);
+#endif
+#undef FA_K7
+}
+
+// K7L: one wavefront per frame (decode_latency.hpp).  A launch with fewer frames than the chip has lanes is latency bound
+// in K7 (one lane per frame: ~1 ms whatever the count).  Returns the call's result, or, with *repeat set, nothing yet:
+// a frame K7L does not take has set the flag and the whole launch is repeated by K7.
+int decode_latency_route(const DecodeRequest& r, const DecodeArgs& a, const LatInline& inl, HeldTasks& held, bool& err_cleared, bool* repeat) {
+    *repeat = false;
+    hipStream_t st = r.st;
+    int* d_err = a.err;
+    const int nch = r.nch;
+    const bool flt = (r.out_float != nullptr);
+    int rc = FA_ERROR_NONE;
+    LatWide wd;
+    std::memset(&wd, 0, sizeof wd);
+    if (nch == 2) {
+        wd.out_i64 = static_cast<int64_t*>(r.out_int); wd.out_f64 = static_cast<double*>(r.out_float);
+        wd.offsets = static_cast<const double*>(r.offsets); wd.gains = static_cast<const double*>(r.gains);
+    }
+    auto launch_latency = [&](const DecodeArgs& aa, int* flag) {
+        const dim3 grid((unsigned)a.n_tasks), block(64);
+        if (nch == 2) {
+            if (flt) hipLaunchKernelGGL((decode_latency_kernel<true, 2>), grid, block, 0, st, aa, inl, wd, flag);
+            else hipLaunchKernelGGL((decode_latency_kernel<false, 2>), grid, block, 0, st, aa, inl, wd, flag);
+        } else {
+            if (flt) hipLaunchKernelGGL((decode_latency_kernel<true, 1>), grid, block, 0, st, aa, inl, wd, flag);
+            else hipLaunchKernelGGL((decode_latency_kernel<false, 1>), grid, block, 0, st, aa, inl, wd, flag);
+        }
+    };
+    const bool verifying = (r.verify < 0 ? g_verify.load() : r.verify != 0);
+    void *pin_h = nullptr, *pin_d = nullptr;
+    void* const h_copy = r.h_copy;
+    const size_t h_copy_bytes = r.h_copy_bytes;
+    // (the caller's own buffer, if it is pinned and device-visible -- fa_pinned_alloc, any hipHostMalloc --, takes
+    // the samples directly whatever their size; otherwise the library's landing buffer, for results up to 512 KB)
+    void* direct = nullptr;
+    if (nch == 1 && h_copy && h_copy_bytes && !verifying) {
+        hipPointerAttribute_t at;
+        // (up to 2 MB: beyond that the kernel's 256-byte stores over the link are slower than one DMA copy out of
+        // the device buffer; at 16 MB the two cost the same, 1.04 ms per 1000-slice read, a quarter of it the Python list of results)
+        if (hipPointerGetAttributes(&at, h_copy) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) {
+            if (h_copy_bytes <= (2u << 20)) direct = at.devicePointer;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    if (nch == 1 && h_copy && h_copy_bytes && (direct || h_copy_bytes <= kPinBytes) && !verifying && pinned_landing(&pin_h, &pin_d)) {
+        // a small read that wants its samples on the host: the kernel stores them and its status word into pinned
+        // host memory; what is left for the host is one synchronisation and a memcpy of a few KB
+        DecodeArgs ap = a;
+        void* const land = direct ? direct : pin_d;
+        if (flt) ap.out_f32 = reinterpret_cast<float*>(land); else ap.out_i32 = reinterpret_cast<int32_t*>(land);
+        volatile int* status = reinterpret_cast<volatile int*>(reinterpret_cast<char*>(pin_h) + kPinBytes);
+        status[0] = 0;
+        int* d_status = reinterpret_cast<int*>(reinterpret_cast<char*>(pin_d) + kPinBytes);
+        prof_begin(2, st);
+        launch_latency(ap, d_status);
+        prof_end(2, st);
+        prof_end(4, st);
+        FA_HIP_TRY(hipStreamSynchronize(st));
+        FA_HIP_TRY(hipGetLastError());
+        if (status[0] == 0) {
+            if (!direct) std::memcpy(h_copy, pin_h, h_copy_bytes);
+            if (r.copied) *r.copied = true;
+            return FA_ERROR_NONE;
+        }
+        // (a frame the latency decoder does not take: the whole launch again, the ordinary way)
+    }
+    if (!err_cleared) { FA_HIP_TRY(hipMemsetAsync(d_err, 0, 32, st)); err_cleared = true; }
+    prof_begin(2, st);
+    launch_latency(a, d_err + 4);
+    prof_end(2, st);
+    prof_end(4, st);
+    int h8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (h_copy && h_copy_bytes) {
+        // a small read wants its samples on the host: they travel with the status words, one synchronisation for both
+        FA_HIP_TRY(hipMemcpyAsync(h_copy, flt ? (const void*)a.out_f32 : (const void*)a.out_i32, h_copy_bytes, hipMemcpyDeviceToHost, st));
+    }
+    FA_HIP_TRY(hipMemcpyAsync(h8, d_err, 32, hipMemcpyDeviceToHost, st));
+    FA_HIP_TRY(hipStreamSynchronize(st));
+    FA_HIP_TRY(hipGetLastError());
+    if (inl.n > 0 && (h8[4] != 0 || verifying) && (rc = held.upload(st))) return rc;  // K7 and the CRC-16 check read the task table from memory
+    if (h8[4] != 0 && std::getenv("FLACARRAY_HIP_LATENCY_DEBUG"))
+        std::fprintf(stderr, "flacarray_hip: latency decoder gave up (reasons %d) on a launch of %lld frames (first slice: stream %lld, sample %lld); repeating with K7\n",
+                     h8[4], (long long)a.n_tasks, (long long)(r.n_slices > 0 ? r.slice_stream[0] : -1), (long long)(r.n_slices > 0 ? r.slice_first[0] : r.first));
+    if (h8[4] != 0) { *repeat = true; return FA_ERROR_NONE; }
+    int h_err[4] = {h8[0], 0, 0, 0};
+    if ((rc = run_verify(a, d_err, h_err, st, r.verify))) return rc;
+    if (r.copied) *r.copied = (h_copy && h_copy_bytes);
+    return h_err[0];
+}
+
+// The decode driver: every device read, every sink.  K6's tables (the index's, or built here for this call), K7's
+// arguments and task table, the K7L attempt, then K7's history passes.
+int decode_device_impl(const DecodeRequest& r) {
+    const bool cmp = (r.first_mismatch != nullptr);
+    const FoldSink* const fold = r.fold;
+    const int nch = r.nch;
+    hipStream_t st = r.st;
+#ifdef FA_DEV_MINIMAL
+    if (cmp || fold) return FA_ERROR_CONVERT_TYPE;
+#endif
+    int verify = cmp ? 0 : r.verify;
+    if (fold && (nch != 1 || cmp)) return FA_ERROR_CONVERT_TYPE;
+    int rc = FA_ERROR_NONE;
+    int h_err[4] = {0, 0, 0, 0};
+    bool err_cleared = true;  // (K6 clears them)
+    DecodeIndex one_off;
+    const DecodeIndex* t = r.idx;
+    if (t) {
+        if (t->nch != nch) return FA_ERROR_DECODE_INIT;
+        err_cleared = false;
+        prof_begin(4, st);
+        // (the status words are cleared where they are first needed: a small read that lands in pinned host memory
+        // never looks at them, and a memset is a launch of its own)
+    } else {
+        if ((rc = build_decode_tables(r.bytes, r.n_bytes, r.starts, r.nbytes, r.n_stream, r.stream_size, nch, st, false, &one_off))) return rc;
+        t = &one_off;
+    }
+    const int64_t n_stream = t->n_stream, stream_size = t->stream_size;
+    const int32_t B = t->B;
+    int* const d_err = t->err;
+
+    // ---- K7's arguments ----
     DecodeArgs a;
     std::memset(&a, 0, sizeof a);
     LatInline inl;
     std::memset(&inl, 0, sizeof inl);
-    std::vector<int64_t> h_tasks;
-    size_t h_tasks_bytes = 0;
-    char* d_tasks = nullptr;
-    bool tasks_uploaded = false;
-    a.blob = d_bytes; a.blob_bytes = n_bytes; a.meta = d_meta; a.ftab = d_ftab; a.nf = nf; a.B = B;
+    HeldTasks held;
+    a.blob = t->bytes; a.blob_bytes = t->n_bytes; a.meta = t->meta; a.ftab = t->ftab; a.nf = t->nf; a.B = B;
     a.stream_size = stream_size;
-    a.out_i32 = d_out_i32; a.out_f32 = d_out_f32; a.offsets = d_offsets; a.gains = d_gains; a.err = d_err;
-    a.cmp = d_cmp; a.first_mismatch = reinterpret_cast<unsigned long long*>(d_first_mismatch);
-    if (cmp) FA_HIP_TRY(hipMemsetAsync(d_first_mismatch, 0xFF, (size_t)n_stream * 8, st));  // -1: no difference (yet)
-    if (n_slices < 0) {
-        a.f0 = first_decode / B;
-        const int64_t f1 = (first_decode + n_decode - 1) / B;
+    a.err = d_err;
+    if (nch == 1) {
+        a.out_i32 = static_cast<int32_t*>(r.out_int); a.out_f32 = static_cast<float*>(r.out_float);
+        a.offsets = static_cast<const float*>(r.offsets); a.gains = static_cast<const float*>(r.gains);
+    }
+    a.cmp = r.cmp; a.first_mismatch = reinterpret_cast<unsigned long long*>(r.first_mismatch);
+    if (cmp) FA_HIP_TRY(hipMemsetAsync(r.first_mismatch, 0xFF, (size_t)n_stream * 8, st));  // -1: no difference (yet)
+    if (r.n_slices < 0) {
+        a.f0 = r.first / B;
+        const int64_t f1 = (r.first + r.n_decode - 1) / B;
         a.nfr = f1 - a.f0 + 1;
-        a.first = first_decode;
-        a.n_decode = n_decode;
+        a.first = r.first;
+        a.n_decode = r.n_decode;
         a.n_tasks = n_stream * a.nfr;
     } else {
         // scattered slices: one task per (slice, frame)
         int64_t n_tasks = 0;
-        for (int64_t i = 0; i < n_slices; ++i) {
-            const int64_t s = slice_stream[i], fst = slice_first[i], cnt = slice_count[i];
+        for (int64_t i = 0; i < r.n_slices; ++i) {
+            const int64_t s = r.slice_stream[i], fst = r.slice_first[i], cnt = r.slice_count[i];
             if (s < 0 || s >= n_stream || fst < 0 || cnt <= 0 || fst + cnt > stream_size) return FA_ERROR_DECODE_SAMPLE_RANGE;
             n_tasks += (fst + cnt - 1) / B - fst / B + 1;
         }
         a.n_tasks = n_tasks;
         if (a.n_tasks == 0) return FA_ERROR_NONE;
-        if (n_tasks <= 8 && B <= kLatMaxBlock && latency_allowed(n_tasks)) {
-            // a handful of frames K7L will take: the task table rides in the kernel arguments (no upload, no
-            // synchronisation).  The conditions are those of the K7L branch below -- a stream with larger blocks goes
-            // straight to K7, which reads the table from memory.
-            int64_t t = 0;
-            for (int64_t i = 0; i < n_slices; ++i) {
-                const int64_t s = slice_stream[i], fst = slice_first[i], cnt = slice_count[i];
-                for (int64_t f = fst / B; f <= (fst + cnt - 1) / B; ++f, ++t) {
-                    inl.stream[t] = s; inl.frame[t] = f; inl.first[t] = fst; inl.last[t] = fst + cnt; inl.out_off[t] = out_offset[i];
-                }
-            }
-            inl.n = (int32_t)n_tasks;
-        }
-        // one staging vector, one copy: [stream | frame | first | last | out offset], each n_tasks long
-        const size_t stp = align_up((size_t)n_tasks * 8, 256);
-        std::vector<int64_t> h(5 * stp / 8);
-        int64_t t = 0;
-        for (int64_t i = 0; i < n_slices; ++i) {
-            const int64_t s = slice_stream[i], fst = slice_first[i], cnt = slice_count[i];
-            for (int64_t f = fst / B; f <= (fst + cnt - 1) / B; ++f, ++t) {
-                h[0 * stp / 8 + t] = s; h[1 * stp / 8 + t] = f; h[2 * stp / 8 + t] = fst; h[3 * stp / 8 + t] = fst + cnt;
-                h[4 * stp / 8 + t] = out_offset[i];
+        // a handful of frames K7L will take: the task table rides in the kernel arguments as well (no upload, no
+        // synchronisation).  The conditions are those of the K7L route below -- a stream with larger blocks goes
+        // straight to K7, which reads the table from memory.
+        const bool ride = (n_tasks <= 8 && B <= kLatMaxBlock && latency_allowed(n_tasks));
+        // one staging vector, one copy
+        std::vector<int64_t> h(task_table_bytes(n_tasks) / 8);
+        int64_t* hc[5];
+        for (int k = 0; k < 5; ++k) hc[k] = h.data() + k * (h.size() / 5);
+        int64_t tk = 0;
+        for (int64_t i = 0; i < r.n_slices; ++i) {
+            const int64_t s = r.slice_stream[i], fst = r.slice_first[i], cnt = r.slice_count[i];
+            for (int64_t f = fst / B; f <= (fst + cnt - 1) / B; ++f, ++tk) {
+                hc[0][tk] = s; hc[1][tk] = f; hc[2][tk] = fst; hc[3][tk] = fst + cnt; hc[4][tk] = r.out_offset[i];
+                if (ride) { inl.stream[tk] = s; inl.frame[tk] = f; inl.first[tk] = fst; inl.last[tk] = fst + cnt; inl.out_off[tk] = r.out_offset[i]; }
             }
         }
-        void* pl = nullptr;
-        if ((rc = task_table_mem(use_index ? idx : nullptr, 5 * stp, &pl))) return rc;
-        char* c = reinterpret_cast<char*>(pl);
-        if (inl.n == 0) {
-            FA_HIP_TRY(hipMemcpyAsync(c, h.data(), 5 * stp, hipMemcpyHostToDevice, st));
+        if (ride) inl.n = (int32_t)n_tasks;
+        int64_t* col[5];
+        if ((rc = task_table_place(r.idx, a, col))) return rc;
+        if (!ride) {
+            FA_HIP_TRY(hipMemcpyAsync(col[0], h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
             FA_HIP_TRY(hipStreamSynchronize(st));  // the host vector goes out of scope
         } else {
-            h_tasks.swap(h);  // (uploaded only if K7 has to repeat the launch)
-            h_tasks_bytes = 5 * stp;
-            d_tasks = c;
+            held.host.swap(h);  // (uploaded only if K7 has to repeat the launch)
+            held.dev = col[0];
         }
-        a.task_stream = reinterpret_cast<const int64_t*>(c + 0 * stp);
-        a.task_frame = reinterpret_cast<const int64_t*>(c + 1 * stp);
-        a.task_first = reinterpret_cast<const int64_t*>(c + 2 * stp);
-        a.task_last = reinterpret_cast<const int64_t*>(c + 3 * stp);
-        a.task_out_off = reinterpret_cast<const int64_t*>(c + 4 * stp);
     }
     if (a.B > kMaxBlock * 16) return FA_ERROR_DECODE_INIT;
-    if (red) {
-        if (n_slices >= 0) return FA_ERROR_CONVERT_TYPE;
-        if (red->find) {
+    if (fold) {
+        if (r.n_slices >= 0) return FA_ERROR_CONVERT_TYPE;
+        const int64_t rows = fold->sel ? fold->n_sel : n_stream;
+        if (fold->kind == FoldSink::kFindCount || fold->kind == FoldSink::kFindFill) {
             // the caller sized its arrays with n_frames frames per row: nothing is written before that is known to hold
-            const FindSink& fs = *red->find;
+            const FindSink& fs = fold->find;
             if (fs.n_frames != a.nfr) return FA_ERROR_CONVERT_TYPE;
-            const int64_t cells = (red->sel ? red->n_sel : n_stream) * a.nfr;
-            if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
+            if ((rows * a.nfr + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
             a.find_lo = fs.lo; a.find_hi = fs.hi; a.find_inside = fs.inside ? 1 : 0;
-            if (fs.hit_ids) {
+            if (fold->kind == FoldSink::kFindFill) {
                 a.find_out = fs.pos; a.find_val = fs.val; a.find_ids = fs.hit_ids; a.find_offs = fs.offs;
             } else {
-                a.find_out = fs.frame_counts; a.find_val = nullptr; a.find_ids = nullptr;
+                a.find_out = fs.frame_counts;
                 a.red_nbins = a.nfr;  // (out_off = row * nfr, as the other folding sinks have row * nbins)
             }
-        } else if (red->hist) {
-            a.hist_counts = red->hist->counts; a.hist_below = red->hist->below; a.hist_above = red->hist->above;
-            a.hist_lo = red->hist->lo; a.hist_shift = red->hist->shift;
-            a.red_width = 0; a.red_nbins = red->nbins;
+        } else if (fold->kind == FoldSink::kHist) {
+            const HistOut& ho = fold->hist;
+            a.hist_counts = ho.counts; a.hist_below = ho.below; a.hist_above = ho.above; a.hist_lo = ho.lo; a.hist_shift = ho.shift;
+            a.red_nbins = ho.nbins;
         } else {
-        a.red_min = red->out.mn; a.red_max = red->out.mx; a.red_sum = red->out.sum;
-        a.red_sq_hi = red->out.sq_hi; a.red_sq_lo = red->out.sq_lo;
-        a.red_width = red->width; a.red_nbins = red->nbins;
+            const ReduceOut& o = fold->red.out;
+            a.red_min = o.mn; a.red_max = o.mx; a.red_sum = o.sum; a.red_sq_hi = o.sq_hi; a.red_sq_lo = o.sq_lo;
+            a.red_width = fold->red.width; a.red_nbins = o.nbins;
         }
-        if (red->sel) a.n_tasks = red->n_sel * a.nfr;  // list mode; the table is built on the device, below
-        if (red->find && red->find->hit_ids) a.n_tasks = red->find->n_hit;  // (the fill pass: the frames with a hit, always a list)
+        if (fold->sel) a.n_tasks = fold->n_sel * a.nfr;  // list mode; the table is built on the device, below
+        if (fold->kind == FoldSink::kFindFill) a.n_tasks = fold->find.n_hit;  // (the frames with a hit, always a list)
         if (a.n_tasks <= 0 || a.n_tasks > (int64_t)64 * 0x7fffffff) return FA_ERROR_DECODE_SAMPLE_RANGE;
-        if (red->find && !red->find->hit_ids) {
-            // (behind every refusal of the arguments: a refused count call has written nothing)
-            const int64_t cells = (red->sel ? red->n_sel : n_stream) * a.nfr;
-            hipLaunchKernelGGL(find_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, red->find->frame_counts, cells);
-            FA_HIP_TRY(hipGetLastError());
-        }
+        if (fold->kind == FoldSink::kFindCount && (rc = find_zero_counts(fold->find, rows * a.nfr, st))) return rc;
     }
-    const unsigned nblk = (unsigned)((a.n_tasks + 63) / 64);
-    const bool f32 = cmp ? (d_offsets != nullptr) : (d_out_f32 != nullptr);
-    const bool f64 = (d_out_f64 != nullptr);
-    if (!cmp && !red && a.B <= kLatMaxBlock && latency_allowed(a.n_tasks)) {
-        LatWide wd;
-        wd.out_i64 = d_out_i64; wd.out_f64 = d_out_f64; wd.offsets = d_offsets64; wd.gains = d_gains64;
-        auto launch_latency = [&](const DecodeArgs& aa, int* flag) {
-            const dim3 grid((unsigned)a.n_tasks), block(64);
-            if (nch == 2) {
-                if (f64) hipLaunchKernelGGL((decode_latency_kernel<true, 2>), grid, block, 0, st, aa, inl, wd, flag);
-                else hipLaunchKernelGGL((decode_latency_kernel<false, 2>), grid, block, 0, st, aa, inl, wd, flag);
-            } else {
-                if (f32) hipLaunchKernelGGL((decode_latency_kernel<true, 1>), grid, block, 0, st, aa, inl, wd, flag);
-                else hipLaunchKernelGGL((decode_latency_kernel<false, 1>), grid, block, 0, st, aa, inl, wd, flag);
-            }
-        };
-        // K7L: one wavefront per frame (decode_latency.hpp).  A launch with fewer frames than the chip has lanes is
-        // latency bound in K7 (one lane per frame: ~1 ms whatever the count); frames K7L does not take set the flag
-        // and the launch is repeated by K7 below.
-        const bool verifying = (verify < 0 ? g_verify.load() : verify != 0);
-        void *pin_h = nullptr, *pin_d = nullptr;
-        // (the caller's own buffer, if it is pinned and device-visible -- fa_pinned_alloc, any hipHostMalloc --, takes
-        // the samples directly whatever their size; otherwise the library's landing buffer, for results up to 512 KB)
-        void* direct = nullptr;
-        if (nch == 1 && h_copy && h_copy_bytes && !verifying) {
-            hipPointerAttribute_t at;
-            // (up to 2 MB: beyond that the kernel's 256-byte stores over the link are slower than one DMA copy out of
-            // the device buffer; at 16 MB the two cost the same, 1.04 ms per 1000-slice read, a quarter of it the Python list of results)
-            if (hipPointerGetAttributes(&at, h_copy) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) {
-                if (h_copy_bytes <= (2u << 20)) direct = at.devicePointer;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        if (nch == 1 && h_copy && h_copy_bytes && (direct || h_copy_bytes <= kPinBytes) && !verifying && pinned_landing(&pin_h, &pin_d)) {
-            // a small read that wants its samples on the host: the kernel stores them and its status word into pinned
-            // host memory; what is left for the host is one synchronisation and a memcpy of a few KB
-            DecodeArgs ap = a;
-            void* const land = direct ? direct : pin_d;
-            if (f32) ap.out_f32 = reinterpret_cast<float*>(land); else ap.out_i32 = reinterpret_cast<int32_t*>(land);
-            volatile int* status = reinterpret_cast<volatile int*>(reinterpret_cast<char*>(pin_h) + kPinBytes);
-            status[0] = 0;
-            int* d_status = reinterpret_cast<int*>(reinterpret_cast<char*>(pin_d) + kPinBytes);
-            prof_begin(2, st);
-            launch_latency(ap, d_status);
-            prof_end(2, st);
-            prof_end(4, st);
-            FA_HIP_TRY(hipStreamSynchronize(st));
-            FA_HIP_TRY(hipGetLastError());
-            if (status[0] == 0) {
-                if (!direct) std::memcpy(h_copy, pin_h, h_copy_bytes);
-                if (h_copied) *h_copied = true;
-                return FA_ERROR_NONE;
-            }
-            // (a frame the latency decoder does not take: the whole launch again, the ordinary way)
-        }
-        if (!err_cleared) { FA_HIP_TRY(hipMemsetAsync(d_err, 0, 32, st)); err_cleared = true; }
-        prof_begin(2, st);
-        launch_latency(a, d_err + 4);
-        prof_end(2, st);
-        prof_end(4, st);
-        int h8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (h_copy && h_copy_bytes) {
-            // a small read wants its samples on the host: they travel with the status words, one synchronisation for both
-            FA_HIP_TRY(hipMemcpyAsync(h_copy, f32 ? (const void*)d_out_f32 : (const void*)d_out_i32, h_copy_bytes, hipMemcpyDeviceToHost, st));
-        }
-        FA_HIP_TRY(hipMemcpyAsync(h8, d_err, 32, hipMemcpyDeviceToHost, st));
-        FA_HIP_TRY(hipStreamSynchronize(st));
-        FA_HIP_TRY(hipGetLastError());
-        if (inl.n > 0 && (h8[4] != 0 || verifying)) {  // K7 and the CRC-16 check read the task table from memory
-            FA_HIP_TRY(hipMemcpyAsync(d_tasks, h_tasks.data(), h_tasks_bytes, hipMemcpyHostToDevice, st));
-            FA_HIP_TRY(hipStreamSynchronize(st));
-            tasks_uploaded = true;
-        }
-        if (h8[4] != 0 && std::getenv("FLACARRAY_HIP_LATENCY_DEBUG"))
-            std::fprintf(stderr, "flacarray_hip: latency decoder gave up (reasons %d) on a launch of %lld frames (first slice: stream %lld, sample %lld); repeating with K7\n",
-                         h8[4], (long long)a.n_tasks, (long long)(n_slices > 0 ? slice_stream[0] : -1), (long long)(n_slices > 0 ? slice_first[0] : first_decode));
-        if (h8[4] == 0) {
-            h_err[0] = h8[0];
-            if ((rc = run_verify(a, d_err, h_err, st, verify))) return rc;
-            if (h_copied) *h_copied = (h_copy && h_copy_bytes);
-            return h_err[0];
-        }
+    if (!cmp && !fold && a.B <= kLatMaxBlock && latency_allowed(a.n_tasks)) {
+        bool repeat = false;
+        rc = decode_latency_route(r, a, inl, held, err_cleared, &repeat);
+        if (!repeat) return rc;
     }
     if (!err_cleared) { FA_HIP_TRY(hipMemsetAsync(d_err, 0, 32, st)); err_cleared = true; }
-    if (inl.n > 0 && !tasks_uploaded) {  // no K7 launch ever sees a task table that only exists in kernel arguments
-        FA_HIP_TRY(hipMemcpyAsync(d_tasks, h_tasks.data(), h_tasks_bytes, hipMemcpyHostToDevice, st));
-        FA_HIP_TRY(hipStreamSynchronize(st));
-        tasks_uploaded = true;
+    // no K7 launch ever sees a task table that only exists in kernel arguments
+    if (inl.n > 0 && !held.uploaded && (rc = held.upload(st))) return rc;
+    if (fold && (fold->kind == FoldSink::kFindFill || fold->sel)) {
+        const int64_t rows = fold->sel ? fold->n_sel : n_stream;
+        int64_t* col[5];
+        if ((rc = task_table_place(r.idx, a, col))) return rc;
+        if (fold->kind == FoldSink::kFindFill)
+            // the frames that hold a hit: task t = cell hit_ids[t], output base offs[cell]
+            hipLaunchKernelGGL(find_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, fold->find.hit_ids, a.n_tasks, rows,
+                               a.nfr, a.f0, a.first, a.first + a.n_decode, fold->sel, n_stream, fold->find.offs, col[0], col[1], col[2], col[3],
+                               col[4], d_err, (int)FA_ERROR_DECODE_SAMPLE_RANGE);
+        else
+            // the named streams: task t = (row t / nfr, frame f0 + t % nfr), output slot row * nbins
+            hipLaunchKernelGGL(reduce_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, fold->sel, n_stream, a.n_tasks,
+                               a.nfr, a.f0, a.first, a.first + a.n_decode, a.red_nbins, col[0], col[1], col[2], col[3], col[4], d_err,
+                               (int)FA_ERROR_DECODE_SAMPLE_RANGE);
     }
-    if (red && red->find && red->find->hit_ids) {
-        // K7's task table for the frames that hold a hit: task t = cell hit_ids[t], output base offs[cell]
-        const size_t stp = align_up((size_t)a.n_tasks * 8, 256);
-        void* pl = nullptr;
-        if ((rc = task_table_mem(use_index ? idx : nullptr, 5 * stp, &pl))) return rc;
-        int64_t* t5[5];
-        for (int k = 0; k < 5; ++k) t5[k] = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(pl) + k * stp);
-        hipLaunchKernelGGL(find_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, red->find->hit_ids, a.n_tasks,
-                           red->sel ? red->n_sel : n_stream, a.nfr, a.f0, a.first, a.first + a.n_decode, red->sel, n_stream, red->find->offs,
-                           t5[0], t5[1], t5[2], t5[3], t5[4], d_err, (int)FA_ERROR_DECODE_SAMPLE_RANGE);
-        a.task_stream = t5[0]; a.task_frame = t5[1]; a.task_first = t5[2]; a.task_last = t5[3]; a.task_out_off = t5[4];
-    } else if (red && red->sel) {
-        // K7's task table for the named streams: task t = (row t / nfr, frame f0 + t % nfr), output slot row * nbins
-        const size_t stp = align_up((size_t)a.n_tasks * 8, 256);
-        void* pl = nullptr;
-        if ((rc = task_table_mem(use_index ? idx : nullptr, 5 * stp, &pl))) return rc;
-        int64_t* t5[5];
-        for (int k = 0; k < 5; ++k) t5[k] = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(pl) + k * stp);
-        hipLaunchKernelGGL(reduce_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, red->sel, n_stream, a.n_tasks, a.nfr,
-                           a.f0, a.first, a.first + a.n_decode, red->nbins, t5[0], t5[1], t5[2], t5[3], t5[4], d_err,
-                           (int)FA_ERROR_DECODE_SAMPLE_RANGE);
-        a.task_stream = t5[0]; a.task_frame = t5[1]; a.task_first = t5[2]; a.task_last = t5[3]; a.task_out_off = t5[4];
-    }
+    const bool f32 = cmp ? (r.offsets != nullptr) : (r.out_float != nullptr);  // (one channel)
 #ifndef FA_DEV_MINIMAL
     if (nch == 2) {
         // two-channel arrays: task-local planar image (low words), bit 32 of every sample, task status
@@ -942,27 +1031,21 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
             hipLaunchKernelGGL(verbatim_channel0_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a);
             a.verbatim_done = 1;
         }
-        // (compare: the same decode, but a frame it rejects marks its stream -- K8C cannot tell a frame abandoned half way)
-        if (cmp) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 2, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+        launch_k7<8, -1>(a, 2, cmp, false, nullptr, st);
         prof_end(2, st);
         FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(hipStreamSynchronize(st));
-        if (h_err[1] & kFlagNeed16) {
-            if (cmp) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 2, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-            else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        }
+        if (h_err[1] & kFlagNeed16) launch_k7<16, 8>(a, 2, cmp, false, nullptr, st);
         if (h_err[1]) {  // a frame left over by the 16-deep pass raises the flag again
             FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
             FA_HIP_TRY(hipStreamSynchronize(st));
         }
-        if (h_err[1] & kFlagNeed32) {
-            if (cmp) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 2, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-            else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        }
-        if (cmp) hipLaunchKernelGGL(compare_channels_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a, d_offsets64, d_gains64);
-        else hipLaunchKernelGGL(combine_channels_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a, d_out_i64, d_out_f64, d_offsets64,
-                                d_gains64);
+        if (h_err[1] & kFlagNeed32) launch_k7<32, 16>(a, 2, cmp, false, nullptr, st);
+        const double* const off64 = static_cast<const double*>(r.offsets);
+        const double* const gain64 = static_cast<const double*>(r.gains);
+        if (cmp) hipLaunchKernelGGL(compare_channels_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a, off64, gain64);
+        else hipLaunchKernelGGL(combine_channels_kernel, dim3((unsigned)a.n_tasks), dim3(256), 0, st, a, static_cast<int64_t*>(r.out_int),
+                                static_cast<double*>(r.out_float), off64, gain64);
         FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(hipStreamSynchronize(st));
         FA_HIP_TRY(hipGetLastError());
@@ -973,8 +1056,7 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
 #endif
     prof_begin(2, st);
 #ifdef FA_DEV_MINIMAL
-    (void)f32;
-    hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    launch_k7<8, -1>(a, 1, cmp, f32, fold, st);
     prof_end(2, st);
     prof_end(4, st);
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
@@ -986,43 +1068,15 @@ int decode_device_impl(const unsigned char* d_bytes, int64_t n_bytes, const int6
     const bool verifying_k7 = (verify < 0 ? g_verify.load() : verify != 0);
     const bool beside = verifying_k7 && a.n_tasks >= 16384 && std::getenv("FLACARRAY_HIP_VERIFY_AFTER") == nullptr &&
                         run_verify_beside_begin(st);
-    if (red && red->find && red->find->hit_ids) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    else if (red && red->find) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    else if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    else if (red) hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    else if (cmp) {
-        if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<8, -1, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    else hipLaunchKernelGGL((decode_frames_kernel<8, -1, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
+    launch_k7<8, -1>(a, 1, cmp, f32, fold, st);
     prof_end(2, st);
     // (queued: the check at the end of this function is not repeated; not queued: it runs there, after K7)
     if (beside && run_verify_beside_launch(a, st)) verify = 0;
     prof_end(4, st);  // (deeper-history passes, when a stream needs them, follow outside this pair)
     FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
-    if (h_err[1] & kFlagNeed16) {
-        if (red && red->find && red->find->hit_ids) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (red && red->find) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (red) hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (cmp) {
-            if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-            else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<16, 8, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else hipLaunchKernelGGL((decode_frames_kernel<16, 8, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    }
-    if (h_err[1] & kFlagNeed32) {
-        if (red && red->find && red->find->hit_ids) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, false, 2>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (red && red->find) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (red && red->hist) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (red) hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, false, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else if (cmp) {
-            if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-            else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1, true>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        } else if (f32) hipLaunchKernelGGL((decode_frames_kernel<32, 16, true, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-        else hipLaunchKernelGGL((decode_frames_kernel<32, 16, false, 1>), dim3(nblk), dim3(64), 0, st, a, d_err + 1);
-    }
+    if (h_err[1] & kFlagNeed16) launch_k7<16, 8>(a, 1, cmp, f32, fold, st);
+    if (h_err[1] & kFlagNeed32) launch_k7<32, 16>(a, 1, cmp, f32, fold, st);
     if (h_err[1]) {
         FA_HIP_TRY(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(hipStreamSynchronize(st));
@@ -1961,14 +2015,12 @@ int fa_decode_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const in
     FA_API_LOCK;
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
-    if ((d_out_i32 == nullptr) == (d_out_f32 == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    if (d_out_f32 && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
-    int64_t first_decode, n_decode;
-    int rc = validate_range(stream_size, first_sample, last_sample, &first_decode, &n_decode);
+    int rc = check_output_args(d_out_i32, d_out_f32, d_offsets, d_gains);
     if (rc) return rc;
-    return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first_decode, n_decode, -1, nullptr,
-                              nullptr, nullptr, nullptr, d_out_i32, d_out_f32, d_offsets, d_gains,
-                              reinterpret_cast<hipStream_t>(stream), 1, nullptr, nullptr, nullptr, nullptr, nullptr, false, verify);
+    DecodeRequest r;
+    if ((rc = validate_range(stream_size, first_sample, last_sample, &r.first, &r.n_decode))) return rc;
+    r.st = reinterpret_cast<hipStream_t>(stream); r.verify = verify;
+    return decode_device_impl(r.store(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size).output(d_out_i32, d_out_f32, d_offsets, d_gains));
 }
 
 int fa_decode_slices_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts,
@@ -1980,11 +2032,12 @@ int fa_decode_slices_i32_device(const unsigned char* d_bytes, int64_t n_bytes, c
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
     if (n_slices <= 0) return FA_ERROR_NONE;
-    if ((d_out_i32 == nullptr) == (d_out_f32 == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    if (d_out_f32 && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
-    return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, 0, 0, n_slices, slice_stream,
-                              slice_first, slice_count, out_offset, d_out_i32, d_out_f32, d_offsets, d_gains,
-                              reinterpret_cast<hipStream_t>(stream), 1, nullptr, nullptr, nullptr, nullptr, nullptr, false, verify);
+    if (const int rc = check_output_args(d_out_i32, d_out_f32, d_offsets, d_gains)) return rc;
+    DecodeRequest r;
+    r.st = reinterpret_cast<hipStream_t>(stream); r.verify = verify;
+    return decode_device_impl(r.store(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size)
+                                  .slices(n_slices, slice_stream, slice_first, slice_count, out_offset)
+                                  .output(d_out_i32, d_out_f32, d_offsets, d_gains));
 }
 
 int fa_decode_index_create(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
@@ -1995,12 +2048,11 @@ int fa_decode_index_create(const unsigned char* d_bytes, int64_t n_bytes, const 
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
     if (channels != 1 && channels != 2) return FA_ERROR_CONVERT_TYPE;
+    if (reinterpret_cast<uintptr_t>(d_bytes) & 15) return FA_ERROR_DECODE_INIT;  // (an index refers to the caller's bytes, not to a realigned copy)
     DecodeIndex* ix = new (std::nothrow) DecodeIndex();
     if (!ix) return FA_ERROR_ALLOC;
     (void)hipGetDevice(&ix->device);
-    const int rc = decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, 0, 0, -1, nullptr, nullptr, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), channels, nullptr, nullptr,
-                                      nullptr, nullptr, ix, true);
+    const int rc = build_decode_tables(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, channels, reinterpret_cast<hipStream_t>(stream), true, ix);
     if (rc) {
         if (ix->meta) (void)hipFree(ix->meta);
         if (ix->ftab) (void)hipFree(ix->ftab);
@@ -2033,29 +2085,17 @@ int fa_decode_indexed(void* index, int64_t first_sample, int64_t last_sample, in
     FA_API_LOCK;
     DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
     if (!ix) return FA_ERROR_DECODE_INIT;
-    {   // an index is used on the device that holds it (its tables, the store and this call's lock are that device's)
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != ix->device) return FA_ERROR_DEVICE;
-    }
-    if ((d_out_int == nullptr) == (d_out_float == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    if (d_out_float && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
-    int64_t first_decode = 0, n_decode = 0;
+    int rc;
+    if ((rc = index_on_device(ix))) return rc;
+    if ((rc = check_output_args(d_out_int, d_out_float, d_offsets, d_gains))) return rc;
+    DecodeRequest r;
     if (n_slices < 0) {
-        const int rc = validate_range(ix->stream_size, first_sample, last_sample, &first_decode, &n_decode);
-        if (rc) return rc;
+        if ((rc = validate_range(ix->stream_size, first_sample, last_sample, &r.first, &r.n_decode))) return rc;
     } else if (n_slices == 0) {
         return FA_ERROR_NONE;
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (ix->nch == 1)
-        return decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, first_decode, n_decode, n_slices, slice_stream, slice_first, slice_count,
-                                  out_offset, reinterpret_cast<int32_t*>(d_out_int), reinterpret_cast<float*>(d_out_float),
-                                  reinterpret_cast<const float*>(d_offsets), reinterpret_cast<const float*>(d_gains), st, 1, nullptr, nullptr,
-                                  nullptr, nullptr, ix, false, verify);
-    return decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, first_decode, n_decode, n_slices, slice_stream, slice_first, slice_count,
-                              out_offset, nullptr, nullptr, nullptr, nullptr, st, 2, reinterpret_cast<int64_t*>(d_out_int),
-                              reinterpret_cast<double*>(d_out_float), reinterpret_cast<const double*>(d_offsets),
-                              reinterpret_cast<const double*>(d_gains), ix, false, verify);
+    r.idx = ix; r.nch = ix->nch; r.st = reinterpret_cast<hipStream_t>(stream); r.verify = verify;
+    return decode_device_impl(r.slices(n_slices, slice_stream, slice_first, slice_count, out_offset).output(d_out_int, d_out_float, d_offsets, d_gains));
 }
 
 void* fa_pinned_alloc(int64_t bytes) {
@@ -2078,26 +2118,16 @@ int fa_decode_indexed_host(void* index, int64_t n_slices, const int64_t* slice_s
     FA_API_LOCK;
     DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
     if (!ix || !h_out || out_bytes < 0) return FA_ERROR_DECODE_INIT;
-    {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != ix->device) return FA_ERROR_DEVICE;
-    }
-    if ((d_out_int == nullptr) == (d_out_float == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    if (d_out_float && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
+    int rc;
+    if ((rc = index_on_device(ix))) return rc;
+    if ((rc = check_output_args(d_out_int, d_out_float, d_offsets, d_gains))) return rc;
     if (n_slices <= 0) return FA_ERROR_NONE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     bool copied = false;
-    int rc;
-    if (ix->nch == 1)
-        rc = decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, n_slices, slice_stream, slice_first, slice_count, out_offset,
-                                reinterpret_cast<int32_t*>(d_out_int), reinterpret_cast<float*>(d_out_float),
-                                reinterpret_cast<const float*>(d_offsets), reinterpret_cast<const float*>(d_gains), st, 1, nullptr, nullptr,
-                                nullptr, nullptr, ix, false, verify, h_out, (size_t)out_bytes, &copied);
-    else
-        rc = decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, n_slices, slice_stream, slice_first, slice_count, out_offset,
-                                nullptr, nullptr, nullptr, nullptr, st, 2, reinterpret_cast<int64_t*>(d_out_int),
-                                reinterpret_cast<double*>(d_out_float), reinterpret_cast<const double*>(d_offsets),
-                                reinterpret_cast<const double*>(d_gains), ix, false, verify);
+    DecodeRequest r;
+    r.idx = ix; r.nch = ix->nch; r.st = st; r.verify = verify;
+    if (ix->nch == 1) { r.h_copy = h_out; r.h_copy_bytes = (size_t)out_bytes; r.copied = &copied; }  // (the landing is K7L's one-channel route's)
+    rc = decode_device_impl(r.slices(n_slices, slice_stream, slice_first, slice_count, out_offset).output(d_out_int, d_out_float, d_offsets, d_gains));
     if (rc) return rc;
     if (!copied && out_bytes > 0) {
         FA_HIP_TRY(hipMemcpyAsync(h_out, d_out_int ? d_out_int : d_out_float, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
@@ -2113,14 +2143,12 @@ int fa_decode_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const in
     FA_API_LOCK;
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
-    if ((d_out_i64 == nullptr) == (d_out_f64 == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    if (d_out_f64 && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
-    int64_t first_decode, n_decode;
-    int rc = validate_range(stream_size, first_sample, last_sample, &first_decode, &n_decode);
+    int rc = check_output_args(d_out_i64, d_out_f64, d_offsets, d_gains);
     if (rc) return rc;
-    return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first_decode, n_decode, -1, nullptr,
-                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream), 2,
-                              d_out_i64, d_out_f64, d_offsets, d_gains, nullptr, false, verify);
+    DecodeRequest r;
+    if ((rc = validate_range(stream_size, first_sample, last_sample, &r.first, &r.n_decode))) return rc;
+    r.nch = 2; r.st = reinterpret_cast<hipStream_t>(stream); r.verify = verify;
+    return decode_device_impl(r.store(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size).output(d_out_i64, d_out_f64, d_offsets, d_gains));
 }
 
 int fa_decode_slices_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts,
@@ -2132,11 +2160,12 @@ int fa_decode_slices_i64_device(const unsigned char* d_bytes, int64_t n_bytes, c
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
     if (n_slices <= 0) return FA_ERROR_NONE;
-    if ((d_out_i64 == nullptr) == (d_out_f64 == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    if (d_out_f64 && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
-    return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, 0, 0, n_slices, slice_stream,
-                              slice_first, slice_count, out_offset, nullptr, nullptr, nullptr, nullptr,
-                              reinterpret_cast<hipStream_t>(stream), 2, d_out_i64, d_out_f64, d_offsets, d_gains, nullptr, false, verify);
+    if (const int rc = check_output_args(d_out_i64, d_out_f64, d_offsets, d_gains)) return rc;
+    DecodeRequest r;
+    r.nch = 2; r.st = reinterpret_cast<hipStream_t>(stream); r.verify = verify;
+    return decode_device_impl(r.store(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size)
+                                  .slices(n_slices, slice_stream, slice_first, slice_count, out_offset)
+                                  .output(d_out_i64, d_out_f64, d_offsets, d_gains));
 }
 
 static int compare_device(int nch, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
@@ -2146,13 +2175,10 @@ static int compare_device(int nch, const unsigned char* d_bytes, int64_t n_bytes
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
     if (!d_data || !d_first_mismatch || (d_offsets == nullptr) != (d_gains == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    const float* off32 = nch == 1 ? static_cast<const float*>(d_offsets) : nullptr;
-    const float* gain32 = nch == 1 ? static_cast<const float*>(d_gains) : nullptr;
-    const double* off64 = nch == 2 ? static_cast<const double*>(d_offsets) : nullptr;
-    const double* gain64 = nch == 2 ? static_cast<const double*>(d_gains) : nullptr;
-    return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, 0, stream_size, -1, nullptr, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, off32, gain32, reinterpret_cast<hipStream_t>(stream), nch, nullptr, nullptr, off64,
-                              gain64, nullptr, false, 0, nullptr, 0, nullptr, d_data, d_first_mismatch);
+    DecodeRequest r;
+    r.nch = nch; r.n_decode = stream_size; r.st = reinterpret_cast<hipStream_t>(stream);
+    r.offsets = d_offsets; r.gains = d_gains; r.cmp = d_data; r.first_mismatch = d_first_mismatch;  // (the sink forces verify to 0)
+    return decode_device_impl(r.store(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size));
 }
 
 int fa_compare_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
@@ -2306,18 +2332,24 @@ int fa_check_md5_device(const unsigned char* d_bytes, int64_t n_bytes, const int
 // ---- binned reduction: min / max / sums of the decoded samples, without a decoded copy -----------------------------
 // One-channel streams: the reducing sink of K7, at every width (profiles/reduce.md).  Two-channel streams: decoded column
 // chunks of whole frames under a cap, each folded into the bins by the chunk reducers.
-// the block size in stream 0's STREAMINFO (chunks are cut at frame boundaries; a header that does not say costs speed only)
-static int reduce_peek_blocksize(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, hipStream_t st, int64_t* B) {
-    *B = 4096;
+// The block size stream 0's STREAMINFO states (minimum = maximum).  Lenient (the two-channel reducers cut their chunks
+// at frame boundaries with it): a header that does not say, or says less than 16, costs speed only -- 4096.  Strict (a
+// search sizes the caller's arrays by the answer): STREAMINFO is the first metadata block, and a header that does not say
+// is FA_ERROR_DECODE_INIT.
+static int peek_blocksize(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, hipStream_t st, bool strict, int64_t* B) {
+    const int miss = strict ? FA_ERROR_DECODE_INIT : FA_ERROR_NONE;
+    if (!strict) *B = 4096;
     int64_t s0 = -1;
     FA_HIP_TRY(hipMemcpyAsync(&s0, d_starts, 8, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
-    if (s0 < 0 || s0 + 12 > n_bytes) return FA_ERROR_NONE;
+    if (s0 < 0 || s0 + 12 > n_bytes) return miss;
     unsigned char h[12];
     FA_HIP_TRY(hipMemcpyAsync(h, d_bytes + s0, 12, hipMemcpyDeviceToHost, st));
     FA_HIP_TRY(hipStreamSynchronize(st));
     const int64_t bmin = ((int64_t)h[8] << 8) | h[9], bmax = ((int64_t)h[10] << 8) | h[11];
-    if (std::memcmp(h, "fLaC", 4) == 0 && bmin == bmax && bmin >= 16) *B = bmin;
+    if (std::memcmp(h, "fLaC", 4) != 0 || bmin != bmax) return miss;
+    if (strict ? ((h[4] & 0x7f) != 0 || bmin <= 0 || bmin > 65535) : bmin < 16) return miss;
+    *B = bmin;
     return FA_ERROR_NONE;
 }
 
@@ -2326,8 +2358,7 @@ static int reduce_peek_blocksize(const unsigned char* d_bytes, int64_t n_bytes, 
 static int reduce_store_args(int nch, DecodeIndex* ix, const unsigned char*& d_bytes, int64_t& n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
                              int64_t& n_stream, int64_t& stream_size, int64_t& first, int64_t& last) {
     if (ix) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != ix->device) return FA_ERROR_DEVICE;
+        if (const int rc = index_on_device(ix)) return rc;
         if (ix->nch != nch) return FA_ERROR_DECODE_INIT;
         n_stream = ix->n_stream; stream_size = ix->stream_size; d_bytes = ix->bytes; n_bytes = ix->n_bytes;
     } else if (!d_bytes || !d_starts || !d_nbytes) {
@@ -2350,7 +2381,7 @@ static int reduce_chunks(DecodeIndex* ix, const unsigned char* d_bytes, int64_t 
     const int64_t n = last - first;
     int rc;
     int64_t B = ix ? ix->B : B_known;
-    if (B <= 0 && (rc = reduce_peek_blocksize(d_bytes, n_bytes, d_starts, st, &B))) return rc;
+    if (B <= 0 && (rc = peek_blocksize(d_bytes, n_bytes, d_starts, st, false, &B))) return rc;
     const int64_t sample_bytes = 8;
     const int64_t cap = max_temp_bytes > 0 ? max_temp_bytes : (int64_t)FA_REDUCE_TEMP_BYTES;
     int64_t cw = cap / (rows * sample_bytes) / B * B;
@@ -2363,16 +2394,17 @@ static int reduce_chunks(DecodeIndex* ix, const unsigned char* d_bytes, int64_t 
         FA_HIP_TRY(hipMemcpyAsync(sl.data(), d_sel, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
         FA_HIP_TRY(hipStreamSynchronize(st));
     }
+    DecodeRequest rq;
+    rq.store(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size);
+    rq.idx = ix; rq.nch = 2; rq.st = st; rq.verify = verify; rq.out_int = d_tmp;
+    if (d_sel) rq.slices(rows, sl.data(), sl.data() + rows, sl.data() + 2 * rows, sl.data() + 3 * rows);
     for (int64_t at = first; at < last;) {
         const int64_t end = std::min(last, at / B * B + cw);  // (chunks after the first start at a frame)
         const int64_t w = end - at;
         if (d_sel)
             for (int64_t r = 0; r < rows; ++r) { sl[rows + r] = at; sl[2 * rows + r] = w; sl[3 * rows + r] = r * w; }
-        rc = decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, at, w, d_sel ? rows : -1, d_sel ? sl.data() : nullptr,
-                                d_sel ? sl.data() + rows : nullptr, d_sel ? sl.data() + 2 * rows : nullptr, d_sel ? sl.data() + 3 * rows : nullptr,
-                                nullptr, nullptr, nullptr, nullptr, st, 2, reinterpret_cast<int64_t*>(d_tmp), nullptr, nullptr, nullptr, ix, false,
-                                verify);
-        if (rc) return rc;
+        rq.first = at; rq.n_decode = w;
+        if ((rc = decode_device_impl(rq))) return rc;
         if ((rc = fold(reinterpret_cast<const long long*>(d_tmp), at, end))) return rc;
         at = end;
     }
@@ -2381,7 +2413,15 @@ static int reduce_chunks(DecodeIndex* ix, const unsigned char* d_bytes, int64_t 
     return FA_ERROR_NONE;
 }
 
-static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+// One-channel stores: [first, last) through K7 into the sink
+static int fold_device(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                       int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, hipStream_t st, int verify, const FoldSink& sink) {
+    DecodeRequest r;
+    r.idx = ix; r.first = first; r.n_decode = last - first; r.st = st; r.verify = verify; r.fold = &sink;
+    return decode_device_impl(r.store(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size));
+}
+
+static int reduce_device(int nch,DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
                          int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t width, int64_t n_sel,
                          const int64_t* d_sel, int64_t max_temp_bytes, int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi,
                          uint64_t* d_sq_lo, void* stream, int verify) {
@@ -2395,19 +2435,16 @@ static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes,
     const int64_t nbins = (n + width - 1) / width;
     const int64_t rows = d_sel ? n_sel : n_stream;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    ReduceSink red;
-    red.width = width; red.nbins = nbins; red.n_sel = n_sel; red.sel = d_sel;
-    red.out.mn = reinterpret_cast<long long*>(d_min); red.out.mx = reinterpret_cast<long long*>(d_max);
-    red.out.sum = reinterpret_cast<long long*>(d_sum);
-    red.out.sq_hi = reinterpret_cast<unsigned long long*>(d_sq_hi); red.out.sq_lo = reinterpret_cast<unsigned long long*>(d_sq_lo);
-    red.out.nbins = nbins;
+    FoldSink sink;
+    sink.kind = FoldSink::kReduce; sink.n_sel = n_sel; sink.sel = d_sel; sink.red.width = width;
+    ReduceOut& out = sink.red.out;
+    out.mn = reinterpret_cast<long long*>(d_min); out.mx = reinterpret_cast<long long*>(d_max); out.sum = reinterpret_cast<long long*>(d_sum);
+    out.sq_hi = reinterpret_cast<unsigned long long*>(d_sq_hi); out.sq_lo = reinterpret_cast<unsigned long long*>(d_sq_lo);
+    out.nbins = nbins;
     const int64_t cells = rows * nbins;
     if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
-    hipLaunchKernelGGL(reduce_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, red.out, cells);
-    if (nch == 1)
-        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, n, -1, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr, 0,
-                                  nullptr, nullptr, nullptr, &red);
+    hipLaunchKernelGGL(reduce_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, out, cells);
+    if (nch == 1) return fold_device(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, st, verify, sink);
     return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, rows, d_sel, max_temp_bytes, st, verify,
                          [&](const long long* tmp, int64_t at, int64_t end) -> int {
         const int64_t w = end - at;
@@ -2415,13 +2452,13 @@ static int reduce_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes,
             const int64_t nseg = (w + kReduceSeg - 1) / kReduceSeg;
             if (rows * nseg > 0x7fffffff) return FA_ERROR_ALLOC;
             const dim3 grid((unsigned)(rows * nseg)), block(64);
-            hipLaunchKernelGGL(reduce_wave_kernel, grid, block, 0, st, tmp, w, at, first, last, width, nseg, red.out);
+            hipLaunchKernelGGL(reduce_wave_kernel, grid, block, 0, st, tmp, w, at, first, last, width, nseg, out);
         } else {
             const int64_t bin_lo = (at - first) / width, n_bin = (end - 1 - first) / width - bin_lo + 1;
             const int64_t nblk = (n_bin + 255) / 256;
             if (rows * nblk > 0x7fffffff) return FA_ERROR_ALLOC;
             const dim3 grid((unsigned)(rows * nblk)), block(256);
-            hipLaunchKernelGGL(reduce_lane_kernel, grid, block, 0, st, tmp, w, at, first, last, width, bin_lo, n_bin, nblk, red.out);
+            hipLaunchKernelGGL(reduce_lane_kernel, grid, block, 0, st, tmp, w, at, first, last, width, bin_lo, n_bin, nblk, out);
         }
         return FA_ERROR_NONE;
     });
@@ -2471,13 +2508,9 @@ static int histogram_device(int nch, DecodeIndex* ix, const unsigned char* d_byt
     if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
     hipLaunchKernelGGL(hist_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, ho, rows);
     if (nch == 1) {
-        ReduceSink red;
-        red.width = last - first; red.nbins = nbins; red.n_sel = n_sel; red.sel = d_sel;
-        red.out = ReduceOut{nullptr, nullptr, nullptr, nullptr, nullptr, nbins};
-        red.hist = &ho;
-        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last - first, -1, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr,
-                                  0, nullptr, nullptr, nullptr, &red);
+        FoldSink sink;
+        sink.kind = FoldSink::kHist; sink.n_sel = n_sel; sink.sel = d_sel; sink.hist = ho;
+        return fold_device(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, st, verify, sink);
     }
     return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, rows, d_sel, max_temp_bytes, st, verify,
                          [&](const long long* tmp, int64_t at, int64_t end) -> int {
@@ -2523,17 +2556,7 @@ int fa_histogram_indexed(void* index, int64_t first, int64_t last, int64_t n_sel
 // metadata block).  A header that does not say is an error here: the caller sizes its arrays by the answer.
 static int find_blocksize(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, hipStream_t st, int64_t* B) {
     if (ix) { *B = ix->B; return ix->B > 0 ? FA_ERROR_NONE : FA_ERROR_DECODE_INIT; }
-    int64_t s0 = -1;
-    FA_HIP_TRY(hipMemcpyAsync(&s0, d_starts, 8, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(hipStreamSynchronize(st));
-    if (s0 < 0 || s0 + 12 > n_bytes) return FA_ERROR_DECODE_INIT;
-    unsigned char h[12];
-    FA_HIP_TRY(hipMemcpyAsync(h, d_bytes + s0, 12, hipMemcpyDeviceToHost, st));
-    FA_HIP_TRY(hipStreamSynchronize(st));
-    const int64_t bmin = ((int64_t)h[8] << 8) | h[9], bmax = ((int64_t)h[10] << 8) | h[11];
-    if (std::memcmp(h, "fLaC", 4) != 0 || (h[4] & 0x7f) != 0 || bmin != bmax || bmin <= 0 || bmin > 65535) return FA_ERROR_DECODE_INIT;
-    *B = bmin;
-    return FA_ERROR_NONE;
+    return peek_blocksize(d_bytes, n_bytes, d_starts, st, true, B);
 }
 
 static int find_plan(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, int64_t stream_size, int64_t first,
@@ -2541,8 +2564,7 @@ static int find_plan(DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_by
     FA_API_LOCK;
     if (!block_size || !n_frames) return FA_ERROR_CONVERT_TYPE;
     if (ix) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess || cur != ix->device) return FA_ERROR_DEVICE;
+        if (const int rc = index_on_device(ix)) return rc;
         stream_size = ix->stream_size;
     } else if (!d_bytes || !d_starts) {
         return FA_ERROR_CONVERT_TYPE;
@@ -2590,13 +2612,9 @@ static int find_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, i
     fs.n_hit = fill ? n_hit : 0; fs.hit_ids = fill ? reinterpret_cast<const long long*>(d_hit) : nullptr;
     fs.offs = reinterpret_cast<const long long*>(d_offs); fs.pos = reinterpret_cast<long long*>(d_pos); fs.val = reinterpret_cast<long long*>(d_val);
     if (nch == 1) {
-        ReduceSink red;
-        red.width = last - first; red.nbins = n_frames; red.n_sel = n_sel; red.sel = d_sel;  // (nbins: the rows' stride in frame_counts)
-        red.out = ReduceOut{nullptr, nullptr, nullptr, nullptr, nullptr, n_frames};
-        red.find = &fs;
-        return decode_device_impl(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last - first, -1, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, nullptr, st, 1, nullptr, nullptr, nullptr, nullptr, ix, false, verify, nullptr,
-                                  0, nullptr, nullptr, nullptr, &red);
+        FoldSink sink;
+        sink.kind = fill ? FoldSink::kFindFill : FoldSink::kFindCount; sink.n_sel = n_sel; sink.sel = d_sel; sink.find = fs;
+        return fold_device(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, st, verify, sink);
     }
     int64_t B = 0;
     if ((rc = find_blocksize(ix, d_bytes, n_bytes, d_starts, st, &B))) return rc;
@@ -2604,10 +2622,7 @@ static int find_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, i
     if (n_frames != nfr) return FA_ERROR_CONVERT_TYPE;
     const int64_t cells = rows * nfr;
     if ((cells + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
-    if (!fill) {
-        hipLaunchKernelGGL(find_zero_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, fs.frame_counts, cells);
-        FA_HIP_TRY(hipGetLastError());
-    }
+    if (!fill && (rc = find_zero_counts(fs, cells, st))) return rc;
     return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, rows, d_sel, max_temp_bytes, st, verify,
                          [&](const long long* tmp, int64_t at, int64_t end) -> int {
         FindChunk c;
@@ -2753,12 +2768,11 @@ static int salvage_run(int nch, const unsigned char* d_bytes, int64_t n_bytes, c
     FA_API_LOCK;
     if (n_stream <= 0) return FA_ERROR_ZERO_NSTREAM;
     if (stream_size <= 0) return FA_ERROR_DECODE_STREAMSIZE;
-    if ((out_int == nullptr) == (out_float == nullptr)) return FA_ERROR_CONVERT_TYPE;
-    if (out_float && (!d_offsets || !d_gains)) return FA_ERROR_CONVERT_TYPE;
+    int rc = check_output_args(out_int, out_float, d_offsets, d_gains);
+    if (rc) return rc;
     if (!fill_value) return FA_ERROR_CONVERT_TYPE;
     int64_t first_decode, n_decode;
-    int rc = validate_range(stream_size, first_sample, last_sample, &first_decode, &n_decode);
-    if (rc) return rc;
+    if ((rc = validate_range(stream_size, first_sample, last_sample, &first_decode, &n_decode))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ScrubTables tb;
     if ((rc = scrub_run(d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, nch, block_size, d_status, st, &tb))) return rc;
@@ -2791,17 +2805,13 @@ static int salvage_run(int nch, const unsigned char* d_bytes, int64_t n_bytes, c
     ix.bytes = tb.bytes; ix.n_bytes = n_bytes; ix.n_stream = n_stream; ix.stream_size = stream_size; ix.nf = nf;
     ix.B = (int32_t)B; ix.nch = nch; ix.meta = tb.meta; ix.ftab = tb.ftab; ix.err = tb.err;
     (void)hipGetDevice(&ix.device);
-    int32_t* o_i32 = nch == 1 ? static_cast<int32_t*>(out_int) : nullptr;
-    float* o_f32 = nch == 1 ? static_cast<float*>(out_float) : nullptr;
-    int64_t* o_i64 = nch == 2 ? static_cast<int64_t*>(out_int) : nullptr;
-    double* o_f64 = nch == 2 ? static_cast<double*>(out_float) : nullptr;
-    const float* off32 = nch == 1 ? static_cast<const float*>(d_offsets) : nullptr;
-    const float* gain32 = nch == 1 ? static_cast<const float*>(d_gains) : nullptr;
-    const double* off64 = nch == 2 ? static_cast<const double*>(d_offsets) : nullptr;
-    const double* gain64 = nch == 2 ? static_cast<const double*>(d_gains) : nullptr;
-    if (fill_off.empty())  // every frame of the range is intact: the ordinary grid-mode decode (the frames were just checked: verify = 0)
-        return decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, first_decode, n_decode, -1, nullptr, nullptr, nullptr, nullptr, o_i32, o_f32,
-                                  off32, gain32, st, nch, o_i64, o_f64, off64, gain64, &ix, false, 0);
+    DecodeRequest r;  // (the frames were just checked: verify = 0)
+    r.idx = &ix; r.nch = nch; r.st = st; r.verify = 0;
+    r.output(out_int, out_float, d_offsets, d_gains);
+    if (fill_off.empty()) {  // every frame of the range is intact: the ordinary grid-mode decode
+        r.first = first_decode; r.n_decode = n_decode;
+        return decode_device_impl(r);
+    }
     {
         const int64_t nr = (int64_t)fill_off.size();
         void* pr = nullptr;
@@ -2817,11 +2827,10 @@ static int salvage_run(int nch, const unsigned char* d_bytes, int64_t n_bytes, c
     }
     if (!sl_stream.empty()) {
         void* pk = nullptr;
-        const size_t task_bytes = 5 * align_up((size_t)n_tasks * 8, 256);
+        const size_t task_bytes = task_table_bytes(n_tasks);
         if ((rc = get_scratch(20, task_bytes + 4096, &pk))) return rc;
         ix.tasks = pk; ix.tasks_bytes = task_bytes + 4096;  // (large enough: the decode never grows, and never owns, this table)
-        rc = decode_device_impl(nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, (int64_t)sl_stream.size(), sl_stream.data(), sl_first.data(), sl_count.data(),
-                                sl_out.data(), o_i32, o_f32, off32, gain32, st, nch, o_i64, o_f64, off64, gain64, &ix, false, 0);
+        rc = decode_device_impl(r.slices((int64_t)sl_stream.size(), sl_stream.data(), sl_first.data(), sl_count.data(), sl_out.data()));
     }
     FA_HIP_TRY(hipStreamSynchronize(st));  // (the fill ranges' host vectors go out of scope)
     return rc;
@@ -2869,15 +2878,6 @@ int fa_reindex_device(const unsigned char* d_old, int64_t n_old_bytes, const int
     if (n_old_bytes <= 0 || !d_old || !d_old_starts || !d_old_nbytes || !d_starts || !d_nbytes) return FA_ERROR_DECODE_INIT;
     if (!d_bytes || capacity_bytes <= 0) return FA_ERROR_ALLOC;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // K6's 16-byte loads are issued relative to the blob base: realign as the decoders do, into their slot (calls are
-    // serialised by api_mu and each writes the slot before it reads it, so one store-sized buffer serves both)
-    if (reinterpret_cast<uintptr_t>(d_old) & 15) {
-        void* al = nullptr;
-        int rc0 = get_scratch(7, (size_t)n_old_bytes + 256, &al);
-        if (rc0) return rc0;
-        FA_HIP_TRY(hipMemcpyAsync(al, d_old, (size_t)n_old_bytes, hipMemcpyDeviceToDevice, st));
-        d_old = reinterpret_cast<const unsigned char*>(al);
-    }
     DecodeIndex ix;
     struct Tables {  // (hipFree waits for the device: the kernels that read the tables are done)
         DecodeIndex* ix;
@@ -2886,9 +2886,11 @@ int fa_reindex_device(const unsigned char* d_old, int64_t n_old_bytes, const int
             if (ix->ftab) (void)hipFree(ix->ftab);
         }
     } tables{&ix};
-    int rc = decode_device_impl(d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, 0, 0, -1, nullptr, nullptr, nullptr, nullptr,
-                                nullptr, nullptr, nullptr, nullptr, st, n_channels, nullptr, nullptr, nullptr, nullptr, &ix, true);
+    // (a store that is not 16-byte aligned is read from K6's realigned copy in the decoders' slot: calls are serialised
+    // by api_mu and each writes the slot before it reads it, so one store-sized buffer serves both)
+    int rc = build_decode_tables(d_old, n_old_bytes, d_old_starts, d_old_nbytes, n_stream, stream_size, n_channels, st, true, &ix);
     if (rc) return rc;  // (K6's own errors: a bad header, variable or mixed block sizes, a walk that runs off its stream)
+    d_old = ix.bytes;
     if (ix.nf > kReindexMaxFrames) return FA_ERROR_DECODE_INIT;
     const int64_t nt = n_stream * ix.nf;
     if (nt >= (1LL << 31) * 256) return FA_ERROR_DECODE_SAMPLE_RANGE;
@@ -3809,16 +3811,10 @@ static int decode_host(const unsigned char* bytes, const int64_t* starts, const 
         const int64_t packed = cr[(size_t)c].packed;
         const char* d_fo = reinterpret_cast<const char*>(d_starts) + (size_t)chunk * 16;  // offsets, gains of the chunk (if any)
         const char* d_fg = reinterpret_cast<const char*>(d_starts) + (size_t)chunk * 24;
-        if (nch == 1)
-            err = decode_device_impl(db, packed, d_starts, d_nb, ns, stream_size, first_decode, n_decode, -1, nullptr, nullptr, nullptr, nullptr,
-                                     offsets ? nullptr : reinterpret_cast<int32_t*>(d_out), offsets ? reinterpret_cast<float*>(d_out) : nullptr,
-                                     offsets ? reinterpret_cast<const float*>(d_fo) : nullptr, offsets ? reinterpret_cast<const float*>(d_fg) : nullptr,
-                                     nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, false, host_verify);
-        else
-            err = decode_device_impl(db, packed, d_starts, d_nb, ns, stream_size, first_decode, n_decode, -1, nullptr, nullptr, nullptr, nullptr,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr, 2, offsets ? nullptr : reinterpret_cast<int64_t*>(d_out),
-                                     offsets ? reinterpret_cast<double*>(d_out) : nullptr, offsets ? reinterpret_cast<const double*>(d_fo) : nullptr,
-                                     offsets ? reinterpret_cast<const double*>(d_fg) : nullptr, nullptr, false, host_verify);
+        DecodeRequest rq;
+        rq.nch = nch; rq.first = first_decode; rq.n_decode = n_decode; rq.verify = host_verify;
+        if (offsets) rq.output(nullptr, d_out, d_fo, d_fg); else rq.out_int = d_out;
+        err = decode_device_impl(rq.store(db, packed, d_starts, d_nb, ns, stream_size));
         if (n_chunks > 1) feed.done_with(c);  // (the decode call ends with a stream synchronisation: the slot is free)
         if (err) break;
         const double td0 = host_now();
