@@ -6,7 +6,7 @@ Drop-in names of the reference (hpc4cmb/flacarray): `array_compress`, `array_dec
 BASELINE.json.  All compute runs in hand-written HIP kernels (libflacarray_hip.so); there is
 no CPU fallback.
 """
-from .array import FlacArray, StreamHistogram, StreamHits, StreamStats
+from .array import CrossStreamStats, FlacArray, StreamHistogram, StreamHits, StreamStats
 from .compress import array_compress
 from .decompress import array_decompress, array_decompress_slice
 from .libflacarray import (
@@ -29,6 +29,7 @@ from .libflacarray import (
     md5_device,
     overwrite_flac_device,
     reduce_flac_device,
+    common_mode_flac_device,
     histogram_flac_device,
     find_flac_device,
     find_counts_flac_device,
@@ -53,6 +54,7 @@ __all__ = [
     "StreamHistogram",
     "StreamHits",
     "StreamStats",
+    "CrossStreamStats",
     "DeviceDecodeIndex",
     "append_flac_device",
     "overwrite_flac_device",
@@ -80,6 +82,7 @@ __all__ = [
     "FRAME_CRC16",
     "compare_flac_device",
     "reduce_flac_device",
+    "common_mode_flac_device",
     "histogram_flac_device",
     "find_flac_device",
     "find_counts_flac_device",

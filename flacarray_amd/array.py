@@ -71,6 +71,11 @@ class _Store:
     gcount = property(lambda s: int(np.prod(s.global_shape[:-1], dtype=np.int64)))
 
 
+def _as_index(streams):
+    """`streams` as the device calls take it: a numpy array (a tensor comes to the host)."""
+    return streams.detach().cpu().numpy() if hasattr(streams, "detach") else np.asarray(streams)
+
+
 def _exact_ratio(num, den):
     """num / den element by element as correctly rounded float64: Python integers divide exactly (object arrays)."""
     out = np.frompyfunc(lambda a, b: int(a) / int(b), 2, 1)(np.asarray(num, dtype=object), np.asarray(den, dtype=object))
@@ -136,6 +141,70 @@ class StreamStats:
         sd = np.sqrt(_exact_ratio(c * q - s * s, c * c))
         if self.gains is not None:
             sd = sd / np.abs(self.gains)
+        return sd
+
+
+@dataclass(frozen=True)
+class CrossStreamStats:
+    """Per-sample statistics ACROSS the streams of each group (FlacArray.common_mode): numpy arrays, G groups, n samples.
+
+    count     int64 [G]: streams in the group.
+    sum       int64 [G, n], equal to np.sum(x[sel_g, first:last], axis=0, dtype=np.int64) of the decoded integers (for a
+              float store the quantised ones): exact for 32-bit stores, modulo 2^64 for 64-bit stores.
+    sumsq_hi, sumsq_lo   uint64 [G, n], 32-bit stores only (None for 64-bit stores): the exact sums of x*x >> 32 and of
+              x*x mod 2^32 over the group's streams, the limbs StreamStats carries.
+    sumsq     float64(sumsq_hi) * 2^32 + float64(sumsq_lo), as StreamStats.sumsq.  None for 64-bit stores.
+    offsets_mean, gain   float64 [G] (a float store whose every group shares one gain; else None): the mean of the
+              group's offsets (math.fsum / count; NaN for an empty group) and the group's gain."""
+
+    count: Any
+    sum: Any
+    sumsq_hi: Any
+    sumsq_lo: Any
+    offsets_mean: Any = None
+    gain: Any = None
+
+    @property
+    def sumsq(self):
+        if self.sumsq_hi is None:
+            return None
+        return np.asarray(self.sumsq_hi).astype(np.float64) * 4294967296.0 + np.asarray(self.sumsq_lo).astype(np.float64)
+
+    def _counts(self):
+        """count broadcast over the samples, and which groups are empty."""
+        c = np.broadcast_to(np.asarray(self.count, dtype=np.int64)[:, None], np.asarray(self.sum).shape)
+        return c, c == 0
+
+    def mean(self):
+        """float64 mean across the group's streams per sample, [G, n], from the exact fields: sum / count, correctly
+        rounded, for an integer store (or a float store read with quantised=True: integer units).  For a float store it
+        is fsum(offsets_g) / count + (sum / count) / gain in float64 -- the mean of offset + x / gain, NOT bit-equal to
+        np.mean over the decoded float32 / float64 streams, whose every sample was rounded on restore.  An empty group
+        gives NaN.  (A 64-bit store whose sum wrapped has no meaningful mean.)"""
+        c, empty = self._counts()
+        m = _exact_ratio(self.sum, np.where(empty, 1, c))
+        if self.gain is not None:
+            m = np.asarray(self.offsets_mean)[:, None] + m / np.asarray(self.gain)[:, None]
+        m[empty] = np.nan
+        return m
+
+    def std(self):
+        """float64 population standard deviation across the group's streams per sample (np.std's ddof = 0), [G, n],
+        without cancellation: count * sum of squares - sum^2 is formed exactly in Python integers, divided by count^2,
+        and the square root taken.  For a float store the result is divided by |gain|: the deviation of x / gain in
+        float64 -- the scatter of the quantised signal about its common mode, the streams' offsets not included -- NOT
+        bit-equal to np.std over the decoded float streams.  An empty group gives NaN.  64-bit stores carry no sum of
+        squares: ValueError."""
+        if self.sumsq_hi is None:
+            raise ValueError("std needs the sum of squares, which 64-bit stores do not carry")
+        c, empty = self._counts()
+        c = np.where(empty, 1, c).astype(object)
+        s = np.asarray(self.sum, dtype=object)
+        q = np.asarray(self.sumsq_hi, dtype=object) * (1 << 32) + np.asarray(self.sumsq_lo, dtype=object)
+        sd = np.sqrt(_exact_ratio(c * q - s * s, c * c))
+        if self.gain is not None:
+            sd = sd / np.abs(np.asarray(self.gain))[:, None]
+        sd[empty] = np.nan
         return sd
 
 
@@ -619,6 +688,63 @@ class FlacArray:
             lo, hi = mn.astype(st.dtype).reshape(shape), mx.astype(st.dtype).reshape(shape)
         limbs = (None, None) if qh is None else (qh.view(np.uint64).reshape(shape), ql.view(np.uint64).reshape(shape))
         return StreamStats(count, lo, hi, sm.reshape(shape), limbs[0], limbs[1], mn.reshape(shape), mx.reshape(shape), off, gain)
+
+    def common_mode(self, groups=None, first=0, last=None, streams=None, quantised=False, verify=None):
+        """Per-sample statistics ACROSS streams without decoding the store into memory (addition to the reference API):
+        for every sample of [first, last) (default: everything; first == last gives arrays of zero columns) the sum, and
+        for 32-bit stores the exact sum of squares, over the streams of each group -- the common mode of a detector
+        time-stream matrix and the scatter about it.  Returns a CrossStreamStats of numpy arrays: count [G], sum [G, n],
+        sumsq_hi / sumsq_lo [G, n], with mean() and std() computed from them on the host.
+
+        `streams`: 1-D flat C-order stream indices with no repeats, as FlacArray.reduce takes them (default: all).
+        `groups`: None for one group, or one integer label in [0, G) per selected stream, G = largest label + 1; labels may
+        come in any order and a label nobody carries is an empty group (count 0, sums 0, mean and std NaN).
+
+        Float stores restore as offset + x / gain, and a sum of quantised integers has a unit only where the group
+        shares one gain bit for bit -- the scalar quanta= case.  There mean() is fsum(offsets_g) / count + (sum / count) /
+        gain and std() is divided by |gain|.  A float store with a group of mixed gains raises ValueError: compress with a
+        scalar quanta=, or pass quantised=True, which returns the integer fields for any store with mean() and std() in
+        integer units.
+
+        int32 / float32 stores are summed inside the decoder (K7X: a wavefront holds the same frame of 64 streams and
+        folds its tile's columns across lanes); int64 / float64 stores through decoded column chunks of at most 256 MiB.
+        Timings against the bare decode and against decode-then-torch: profiles/common_mode.md.  Uses the resident store
+        and its decode index after to_device(), and uploads the store otherwise.  `verify`: the decoder's frame CRC-16
+        check (None: the process default).  Decode failures raise the decoder's RuntimeError."""
+        import math
+
+        from .libflacarray import _xsum_args, common_mode_flac_device
+
+        st = self._st
+        first, last, G, order, _, count = _xsum_args(st.count, st.samples, groups, None, first, last, streams, not st.wide, st.wide)
+        off_mean = gain = None
+        if st.offsets is not None and not quantised:
+            # the check needs no GPU: it stands in front of the decode
+            offs = np.asarray(st.offsets).reshape(-1)[order]
+            gains = np.asarray(st.gains).reshape(-1)[order]
+            ends = np.cumsum(count)
+            off_mean, gain = np.full(G, np.nan), np.full(G, np.nan)
+            for g in range(G):
+                gg = gains[ends[g] - count[g] : ends[g]]
+                if gg.size == 0:
+                    continue
+                bits = np.ascontiguousarray(gg).view("u%d" % gg.dtype.itemsize)  # (bit for bit: -0.0 and NaN included)
+                if not np.all(bits == bits[0]):
+                    raise ValueError(f"group {g} mixes gains: a sum of quantised integers has no unit there -- compress with a scalar "
+                                     "quanta=, or pass quantised=True for the integer sums")
+                off_mean[g] = math.fsum(float(v) for v in offs[ends[g] - count[g] : ends[g]]) / int(count[g])
+                gain[g] = float(gg[0])
+        # (the plan is made again from the same arguments by the device call: it is cheap and pure)
+        idx = None if streams is None else _as_index(streams)
+        if self._resident is not None:
+            out = self._index().common_mode(groups, G, first, last, streams=idx, verify=verify)
+        else:
+            _, comp, starts, nbytes = self._device_store()
+            out = common_mode_flac_device(comp, starts, nbytes, st.samples, groups, G, first, last, streams=idx, squares=not st.wide,
+                                          is_int64=st.wide, verify=verify)
+        sm, qh, ql = (None if t is None else t.cpu().numpy() for t in out)
+        limbs = (None, None) if qh is None else (qh.view(np.uint64), ql.view(np.uint64))
+        return CrossStreamStats(count, sm, limbs[0], limbs[1], off_mean, gain)
 
     # ---- distributions: value histogram and exact order statistics from the compressed store ----
     def _hist_pass(self, store, lo, shift, nbins, first, last, idx):

@@ -503,10 +503,10 @@ struct DecodeArgs {
     // outputs.  (The unions: the reducing sink, which has no use for the store's, the restore's, the two-channel image's or
     // the compare sink's arguments, keeps its own in their places -- the layout, and with it the code of every other
     // instantiation, is what it was without that sink.)
-    union { int32_t* out_i32; long long* red_min; unsigned long long* hist_counts; long long* find_out; };
+    union { int32_t* out_i32; long long* red_min; unsigned long long* hist_counts; long long* find_out; long long* xs_sum; };
     union { float* out_f32; long long* red_max; unsigned long long* hist_below; long long* find_val; };                 // when non-null: dequantised output instead of out_i32
-    union { const float* offsets; long long* red_sum; unsigned long long* hist_above; const long long* find_lo; };           // per stream
-    union { const float* gains; unsigned long long* red_sq_hi; const long long* hist_lo; const long long* find_hi; };
+    union { const float* offsets; long long* red_sum; unsigned long long* hist_above; const long long* find_lo; unsigned long long* xs_sq_hi; };           // per stream
+    union { const float* gains; unsigned long long* red_sq_hi; const long long* hist_lo; const long long* find_hi; unsigned long long* xs_sq_lo; };
     int* err;
     // two-channel arrays (NCH == 2): out_i32 is then the task-local planar image
     union { uint32_t* hibits; unsigned long long* red_sq_lo; const int32_t* hist_shift; const long long* find_ids; };   // [n_tasks][2][hib_words] bit 32 of every sample
@@ -533,6 +533,11 @@ struct DecodeArgs {
     // that array; its k-th hit goes to find_out[base + k] (the sample's index in the stream) and, when find_val is not
     // null, find_val[base + k] (its value), base = task_out_off[t] = find_offs[find_ids[t]], the exclusive prefix sum of
     // the counts (cells + 1 entries); a lane writes at most find_offs[id + 1] - find_offs[id] hits.
+    // cross-stream sink (decode_frames_kernel<..., XSUM = true>; one channel, list mode), K7X: the task table puts ONE frame
+    // of 64 streams of one group into every wave (xsum_tasks_kernel) and task_out_off carries group * (last - first); the
+    // samples [first, last) of the wave's live lanes are added, column by column, to xs_sum[group * n + sample - first] and
+    // the radix-2^32 limbs of their squares to xs_sq_hi / xs_sq_lo (null together: no squares).  The arrays hold zeros
+    // before the first launch.
     union { const void* cmp; int64_t red_width; int64_t find_inside; };
     union { unsigned long long* first_mismatch; int64_t red_nbins; const long long* find_offs; };
 };
@@ -584,6 +589,12 @@ __device__ __forceinline__ void static_for(F&& f) {
 #endif
 #ifndef FA_K7_VOTE
 #define FA_K7_VOTE 1  // one wave vote per refill round replaces the prefetch's four per-piece bounds (profiles/k7_refill.md)
+#endif
+#ifndef FA_XSUM_MUTANT
+#define FA_XSUM_MUTANT 0  // test-the-tests builds only (results are wrong, every access stays in bounds; profiles/common_mode.md): K7X
+                          // 1 = folds every row, live or not, 2 = does not restore wasted bits, 4 = adds columns outside the valid
+                          // range to its nearest end, 32 = does not combine the halves; 8 = xsum_tasks_kernel gives padding lanes
+                          // the range; 16 = the driver does not zero-fill
 #endif
 #ifndef FA_K7_X
 #define FA_K7_X 0  // timing experiments only (results are wrong): 1 = no prediction, 2 = no global stores, 4 = no tile write,
@@ -814,7 +825,13 @@ __device__ __noinline__ BitsRet slow_sample(const uint8_t* cbase, const uint8_t*
 // with one plain 8-byte store per frame, by the one pass that decodes the frame.  FIND = 2 fills: the lane writes the
 // position (and value) of its k-th hit behind its frame's base.  Hits are rare in what this is for, so the fill tests
 // __any(hit) before its divergent stores; no atomics in either, so nothing depends on the order of arrival.
-template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false, bool HIST = false, int FIND = 0>
+// XSUM (one channel, integers): the cross-stream sink, K7X -- the one sink that folds ACROSS lanes.  Not a FOLD sink: it
+// keeps the tile image exactly as the storing int32 instantiation does (the same LDS, the same waves per CU) and replaces
+// the cooperative store of flush_tile by a column fold: the wave holds the same frame of 64 streams, so the 64 rows of a
+// tile column are one sample index of 64 streams.  Their sum and the two limbs of their squares are added to the result
+// with 64-bit relaxed atomics of agent scope onto zeroed arrays (integer adds commute, as for K7H).  Only the rows live
+// in this <MO, MO_DONE> pass are folded -- the other rows of the tile hold leftovers -- so the passes add up to the whole.
+template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false, bool HIST = false, int FIND = 0, bool XSUM = false>
 #ifndef FA_K7_WAVES_ATTR
 #define FA_K7_WAVES_ATTR
 #endif
@@ -828,6 +845,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     static_assert(!RED || (NCH == 1 && !F32 && !CMP), "reducing sink: one channel, integer domain");
     static_assert(!HIST || (NCH == 1 && !F32 && !CMP && !RED), "histogram sink: one channel, integer domain");
     static_assert(FIND == 0 || (NCH == 1 && !F32 && !CMP && !RED && !HIST), "search sink: one channel, integer domain");
+    static_assert(!XSUM || (NCH == 1 && !F32 && !CMP && !RED && !HIST && FIND == 0), "cross-stream sink: one channel, integer domain");
+    static_assert(!XSUM || kTileW == 32, "cross-stream sink: a lane owns one of 32 tile columns and one half of the 64 rows");
     constexpr bool FOLD = RED || HIST || FIND != 0;  // no tile image, no cooperative store: every sample goes to the sink from its register
     constexpr bool SINK = CMP && NCH == 1;  // the tile store compares instead of writing
     // one LDS object, so that the ring image starts at LDS address 0 (ring_words builds its addresses with an OR)
@@ -1192,7 +1211,7 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     // the LDS saved is what lets more waves share a CU); the valid range is fetched in the rare clipped path.
     int64_t rout[kTileG];
 #pragma unroll
-    for (int it = 0; it < (FOLD ? 0 : kTileG); ++it) {
+    for (int it = 0; it < ((FOLD || XSUM) ? 0 : kTileG); ++it) {
         const int r = it * (64 / kTileG) + (lane / kTileG);
         const uint32_t rl = (uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)(uint32_t)(uint64_t)row0);
         const uint32_t rh = (uint32_t)__builtin_amdgcn_ds_bpermute(r << 2, (int)(uint32_t)((uint64_t)row0 >> 32));
@@ -1225,6 +1244,21 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     // wasted bits are rare: the sample loop stores unshifted values and the tile flush restores the shift of each
     // row's frame only when some lane of the wave has one (wave-uniform branch)
     const bool any_wasted = __any(wasted != 0);
+    // K7X: the rows this pass decodes and delivers -- not idle, not deferred to a deeper pass, not done by an earlier one,
+    // not rejected, not padding (a padding lane has an empty range) -- as a wave-uniform mask; their common valid range
+    // (the wave holds one frame of 64 streams, one [first, last)) and output index of frame sample 0, from the first of them
+    uint64_t xs_live = 0;
+    int xs_lo = 0, xs_hi = 0;
+    int64_t xs_row0 = 0;
+    if constexpr (XSUM) {
+        xs_live = __ballot(mode != 3 && hi > lo);
+        const int fl = xs_live ? __ffsll((unsigned long long)xs_live) - 1 : 0;
+        xs_lo = __builtin_amdgcn_readfirstlane(__shfl(lo, fl, 64));
+        xs_hi = __builtin_amdgcn_readfirstlane(__shfl(hi, fl, 64));
+        const uint32_t r0l = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)(uint32_t)(uint64_t)row0, fl, 64));
+        const uint32_t r0h = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)(uint32_t)((uint64_t)row0 >> 32), fl, 64));
+        xs_row0 = (int64_t)(((uint64_t)r0h << 32) | r0l);
+    }
     // chunk `pend_ci` is requested one chunk-time before it is stored into the ring
     uint32_t pend_ci = next_chunk;
     Chunk pend = chunk_fetch(cbase, lim16, pend_ci);
@@ -1544,6 +1578,68 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     auto flush_tile = [&](int tbase) __attribute__((always_inline)) {
         if constexpr (FOLD) return;  // (no tile)
         __builtin_amdgcn_wave_barrier();
+        if constexpr (XSUM) {
+            // K7X: the column fold in place of the store.  Lane l owns tile column t = l % 32 and the rows (decoder lanes) of
+            // its half, l / 32.  Column t of the tile starts at word t * 64, so lanes that walked rows 0, 1, 2, ... in step
+            // would hit one bank with all 32 lanes of a half (ds_read_b32: two groups of 32 lanes, bank = word mod 32).  At
+            // step j lane l reads PHYSICAL word (j + t) mod 32 of its half of the column -- 32 lanes, 32 banks -- and the
+            // tile's XOR swizzle, undone, names the row that word belongs to: r = word ^ ((t >> 2) * kTileSwz).
+            if (xs_live != 0ull && tbase < xs_hi && tbase + kTileW > xs_lo) {
+                const int t = lane & 31, half = lane >> 5;
+#if (FA_XSUM_MUTANT & 4)
+                const int col = tbase + t < xs_lo ? xs_lo : tbase + t >= xs_hi ? xs_hi - 1 : tbase + t;
+                const bool colv = true;
+#else
+                const int col = tbase + t;
+                const bool colv = col >= xs_lo && col < xs_hi;  // (a partial tile: the range's ends, a short last frame)
+#endif
+#if (FA_XSUM_MUTANT & 1)
+                const uint32_t lm = 0xffffffffu;
+#else
+                const uint32_t lm = half ? (uint32_t)(xs_live >> 32) : (uint32_t)xs_live;
+#endif
+                const int swz = (t >> 2) * kTileSwz;
+                const int32_t* const tcol = tile + t * kLaneStride + half * 32;
+                const bool sq = a.xs_sq_hi != nullptr;
+                int64_t sm = 0;
+                uint64_t qh = 0, ql = 0;
+#pragma unroll 8
+                for (int j = 0; j < 32; ++j) {
+                    const int pw = (j + t) & 31;
+                    const int r = pw ^ swz;
+                    int32_t v = tcol[pw];
+                    // (wave-uniform, and the exchange stands outside every divergent branch)
+#if !(FA_XSUM_MUTANT & 2)
+                    if (__builtin_expect(any_wasted, 0)) v = (int32_t)((uint32_t)v << __builtin_amdgcn_ds_bpermute((half * 32 + r) << 2, wasted));
+#endif
+                    const int64_t x = ((lm >> r) & 1u) ? (int64_t)v : 0;  // live rows only: the others hold leftovers
+                    sm += x;
+                    if (sq) {
+                        const uint64_t q = (uint64_t)(x * x);  // <= 2^62
+                        ql += (uint32_t)q;
+                        qh += q >> 32;
+                    }
+                }
+                // the two halves meet
+#if !(FA_XSUM_MUTANT & 32)
+                sm += __shfl_xor((long long)sm, 32, 64);
+                if (sq) {
+                    ql += __shfl_xor((unsigned long long)ql, 32, 64);
+                    qh += __shfl_xor((unsigned long long)qh, 32, 64);
+                }
+#endif
+                if (half == 0 && colv) {
+                    const int64_t o = xs_row0 + col;
+                    (void)__hip_atomic_fetch_add(a.xs_sum + o, (long long)sm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (sq) {
+                        (void)__hip_atomic_fetch_add(a.xs_sq_hi + o, (unsigned long long)qh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        (void)__hip_atomic_fetch_add(a.xs_sq_lo + o, (unsigned long long)ql, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            return;
+        }
         if constexpr (NCH == 2) {
             // bit 32 of this lane's 32 samples (tiles are 32 samples wide)
             if (tbase < hi && tbase + kTileW > lo) a.hibits[(task * 2 + chn) * (int64_t)a.hib_words + (tbase >> 5)] = hbw;

@@ -42,6 +42,7 @@
 #include "reduce_kernels.hpp"
 #include "histogram_kernels.hpp"
 #include "find_kernels.hpp"
+#include "xsum_kernels.hpp"
 #include "scrub_kernels.hpp"
 #include "reindex_kernels.hpp"
 #include "window_kernels.hpp"
@@ -563,18 +564,20 @@ struct DecodeIndex {
     int device = -1;
 };
 
-// A folding sink of K7 (one channel: fa_reduce_*, fa_histogram_*, fa_find_*): what the decoded samples of the range are
-// folded into where an output would stand.  The rows of the result are all streams (sel == nullptr) or the n_sel streams
-// a device array names; the caller's arrays hold the identities, except the find count's, which the driver zeroes.
+// A folding sink of K7 (one channel: fa_reduce_*, fa_histogram_*, fa_find_*, fa_xsum_*): what the decoded samples of the
+// range are folded into where an output would stand.  The rows of the result are all streams (sel == nullptr) or the n_sel
+// streams a device array names; the caller's arrays hold the identities, except the find count's and the cross-stream
+// sums', which the drivers zero.  kXsum: sel is the selection sorted by group (always given) and the rows are its groups.
 struct ReduceBins { int64_t width; ReduceOut out; };
 struct FoldSink {
-    enum Kind { kReduce, kHist, kFindCount, kFindFill } kind;
+    enum Kind { kReduce, kHist, kFindCount, kFindFill, kXsum } kind;
     int64_t n_sel;
     const int64_t* sel;
     union {
         ReduceBins red;  // kReduce: red.out.nbins bins of `width` samples per row
         HistOut hist;    // kHist (K7H): hist.nbins value bins per row
         FindSink find;   // kFindCount, kFindFill (K7F): frame_counts, or hit_ids / offs / pos / val
+        XsumSink xsum;   // kXsum (K7X): the plan's row table and sum / sq_hi / sq_lo [n_groups][n]
     };
 };
 
@@ -770,6 +773,7 @@ void launch_k7(const DecodeArgs& a, int nch, bool cmp, bool f32, const FoldSink*
     else if (fold && fold->kind == FoldSink::kFindFill) FA_K7(false, 1, false, false, false, 2);
     else if (fold && fold->kind == FoldSink::kFindCount) FA_K7(false, 1, false, false, false, 1);
     else if (fold && fold->kind == FoldSink::kHist) FA_K7(false, 1, false, false, true);
+    else if (fold && fold->kind == FoldSink::kXsum) FA_K7(false, 1, false, false, false, 0, true);
     else if (fold) FA_K7(false, 1, false, true);
     else if (cmp) { if (f32) FA_K7(true, 1, true); else FA_K7(false, 1, true); }
     else if (f32) FA_K7(true, 1);
@@ -973,6 +977,10 @@ int decode_device_impl(const DecodeRequest& r) {
                 a.find_out = fs.frame_counts;
                 a.red_nbins = a.nfr;  // (out_off = row * nfr, as the other folding sinks have row * nbins)
             }
+        } else if (fold->kind == FoldSink::kXsum) {
+            const XsumSink& xs = fold->xsum;
+            if (!fold->sel || xs.n_rows <= 0 || xs.n_rows > 0x7fffffff / a.nfr) return FA_ERROR_DECODE_SAMPLE_RANGE;
+            a.xs_sum = xs.sum; a.xs_sq_hi = xs.sq_hi; a.xs_sq_lo = xs.sq_lo;
         } else if (fold->kind == FoldSink::kHist) {
             const HistOut& ho = fold->hist;
             a.hist_counts = ho.counts; a.hist_below = ho.below; a.hist_above = ho.above; a.hist_lo = ho.lo; a.hist_shift = ho.shift;
@@ -984,6 +992,7 @@ int decode_device_impl(const DecodeRequest& r) {
         }
         if (fold->sel) a.n_tasks = fold->n_sel * a.nfr;  // list mode; the table is built on the device, below
         if (fold->kind == FoldSink::kFindFill) a.n_tasks = fold->find.n_hit;  // (the frames with a hit, always a list)
+        if (fold->kind == FoldSink::kXsum) a.n_tasks = fold->xsum.n_rows * a.nfr * 64;  // (a wave per plan row and frame)
         if (a.n_tasks <= 0 || a.n_tasks > (int64_t)64 * 0x7fffffff) return FA_ERROR_DECODE_SAMPLE_RANGE;
         if (fold->kind == FoldSink::kFindCount && (rc = find_zero_counts(fold->find, rows * a.nfr, st))) return rc;
     }
@@ -1004,6 +1013,11 @@ int decode_device_impl(const DecodeRequest& r) {
             hipLaunchKernelGGL(find_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, fold->find.hit_ids, a.n_tasks, rows,
                                a.nfr, a.f0, a.first, a.first + a.n_decode, fold->sel, n_stream, fold->find.offs, col[0], col[1], col[2], col[3],
                                col[4], d_err, (int)FA_ERROR_DECODE_SAMPLE_RANGE);
+        else if (fold->kind == FoldSink::kXsum)
+            // one frame of the 64 streams of a plan row per wave, output offset group * n
+            hipLaunchKernelGGL(xsum_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, fold->sel, fold->n_sel,
+                               fold->xsum.rows, fold->xsum.n_rows, fold->xsum.n_groups, n_stream, a.nfr, a.f0, a.first, a.first + a.n_decode,
+                               col[0], col[1], col[2], col[3], col[4], d_err, (int)FA_ERROR_DECODE_SAMPLE_RANGE);
         else
             // the named streams: task t = (row t / nfr, frame f0 + t % nfr), output slot row * nbins
             hipLaunchKernelGGL(reduce_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, fold->sel, n_stream, a.n_tasks,
@@ -2484,6 +2498,75 @@ int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, i
     if (!ix) return FA_ERROR_DECODE_INIT;
     return reduce_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, width, n_sel, d_sel_streams, max_temp_bytes, d_min, d_max,
                          d_sum, d_sq_hi, d_sq_lo, stream, verify);
+}
+
+// ---- fold across streams: per-sample sums over groups of streams, without a decoded copy (profiles/common_mode.md) -----
+// One-channel streams: the cross-stream sink of K7 (K7X), a wave per (plan row, frame).  Two-channel streams: the column
+// chunks of the binned reduction, each summed by xsum_chunk_kernel.  The result arrays are zero-filled here, behind every
+// refusal of the arguments: a refused call has written nothing.
+static int xsum_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                       int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                       const int64_t* d_rows, int64_t n_groups, int64_t max_temp_bytes, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo,
+                       void* stream, int verify) {
+    FA_API_LOCK;
+    int rc;
+    if ((rc = reduce_store_args(nch, ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last))) return rc;
+    if (!d_sum || (d_sq_hi == nullptr) != (d_sq_lo == nullptr) || (nch == 2 && d_sq_hi)) return FA_ERROR_CONVERT_TYPE;
+    if (n_groups < 1 || n_sel < 0 || n_rows < 0 || n_sel > n_stream || n_rows > n_sel || (n_sel > 0 && (!d_order || !d_rows || n_rows < 1)))
+        return FA_ERROR_CONVERT_TYPE;
+    const int64_t n = last - first;
+    if (n_groups > INT64_MAX / 8 / n) return FA_ERROR_ALLOC;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t cells_b = (size_t)n_groups * (size_t)n * 8;
+#if !(FA_XSUM_MUTANT & 16)
+    FA_HIP_TRY(hipMemsetAsync(d_sum, 0, cells_b, st));
+    if (d_sq_hi) {
+        FA_HIP_TRY(hipMemsetAsync(d_sq_hi, 0, cells_b, st));
+        FA_HIP_TRY(hipMemsetAsync(d_sq_lo, 0, cells_b, st));
+    }
+#else
+    (void)cells_b;
+#endif
+    if (n_sel == 0) return FA_ERROR_NONE;  // (every group is empty)
+    if (nch == 1) {
+        FoldSink sink;
+        sink.kind = FoldSink::kXsum; sink.n_sel = n_sel; sink.sel = d_order;
+        sink.xsum.n_rows = n_rows; sink.xsum.rows = d_rows; sink.xsum.n_groups = n_groups;
+        sink.xsum.sum = reinterpret_cast<long long*>(d_sum);
+        sink.xsum.sq_hi = reinterpret_cast<unsigned long long*>(d_sq_hi); sink.xsum.sq_lo = reinterpret_cast<unsigned long long*>(d_sq_lo);
+        return fold_device(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, st, verify, sink);
+    }
+    return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_order, max_temp_bytes, st, verify,
+                         [&](const long long* tmp, int64_t at, int64_t end) -> int {
+        const int64_t w = end - at;
+        if ((w + 255) / 256 > 0x7fffffff) return FA_ERROR_ALLOC;
+        const dim3 grid((unsigned)((w + 255) / 256), (unsigned)std::min<int64_t>(n_groups, 65535)), block(256);
+        hipLaunchKernelGGL(xsum_chunk_kernel, grid, block, 0, st, tmp, w, at, first, n, n_sel, d_rows, n_rows, n_groups,
+                           reinterpret_cast<long long*>(d_sum));
+        return FA_ERROR_NONE;
+    });
+}
+
+int fa_xsum_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                       int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                       const int64_t* d_rows, int64_t n_groups, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify) {
+    return xsum_device(1, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_order, n_rows, d_rows, n_groups,
+                       0, d_sum, d_sq_hi, d_sq_lo, stream, verify);
+}
+
+int fa_xsum_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                       int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                       const int64_t* d_rows, int64_t n_groups, int64_t max_temp_bytes, int64_t* d_sum, void* stream, int verify) {
+    return xsum_device(2, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_order, n_rows, d_rows, n_groups,
+                       max_temp_bytes, d_sum, nullptr, nullptr, stream, verify);
+}
+
+int fa_xsum_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows, const int64_t* d_rows,
+                    int64_t n_groups, int64_t max_temp_bytes, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify) {
+    DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
+    if (!ix) return FA_ERROR_DECODE_INIT;
+    return xsum_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, n_sel, d_order, n_rows, d_rows, n_groups, max_temp_bytes, d_sum,
+                       d_sq_hi, d_sq_lo, stream, verify);
 }
 
 // ---- value histogram: counts per value bin of every row, without a decoded copy (profiles/histogram.md) ----------------

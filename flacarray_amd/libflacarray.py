@@ -1404,6 +1404,121 @@ def reduce_flac_device(compressed, starts, nbytes, stream_size, width=None, firs
     return mn, mx, sm, qh, ql
 
 
+def xsum_plan(labels, n_groups):
+    """The host plan of a fold across streams (pure: no GPU).  `labels[i]` in [0, n_groups) is the group of the i-th selected
+    stream.  Returns (perm, rows, count): `perm` (int64) the positions 0..len(labels)-1 stable-sorted by label, so that a
+    group's streams are adjacent and keep the caller's order; `rows` (int64 [n_rows, 3]) one entry per 64 lanes of one
+    group -- [group, first position in perm, real lanes (1..64)] -- each group padded to a multiple of 64 lanes and an
+    empty group having no row; `count` (int64 [n_groups]) the streams per group."""
+    lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+    n_groups = int(n_groups)
+    if n_groups < 1:
+        raise ValueError("n_groups should be at least 1")
+    if lab.size and (lab.min() < 0 or lab.max() >= n_groups):
+        raise ValueError(f"groups holds a label outside [0, {n_groups})")
+    perm = np.argsort(lab, kind="stable").astype(np.int64)
+    count = np.bincount(lab, minlength=n_groups).astype(np.int64)
+    start = np.concatenate([[0], np.cumsum(count)[:-1]]).astype(np.int64)
+    rows = [(g, int(start[g]) + at, min(64, int(count[g]) - at)) for g in range(n_groups) for at in range(0, int(count[g]), 64)]
+    return perm, np.asarray(rows, dtype=np.int64).reshape(-1, 3), count
+
+
+def _xsum_args(n_stream, stream_size, groups, n_groups, first_sample, last_sample, streams, squares, is_int64):
+    """The argument checks of the fold across streams (ValueError, before anything touches the GPU).  Returns (first, last,
+    n_groups, order, rows, count): `order` the selected stream indices sorted by group and `rows` the plan's row table
+    (xsum_plan), int64 numpy arrays.  Unlike the reductions along a stream, an empty range first == last is accepted."""
+    stream_size = int(stream_size)
+    if stream_size <= 0:
+        raise ValueError("You must specify the non-zero stream size")
+    first = int(first_sample)
+    last = stream_size if last_sample is None else int(last_sample)
+    if first < 0 or last > stream_size or first > last:
+        raise ValueError(f"samples [{first}, {last}) are not a range inside streams of {stream_size} samples")
+    if squares and is_int64:
+        raise ValueError("two-channel (64-bit) stores carry no sum of squares: pass squares=False")
+    idx = _stream_indices(streams, n_stream)
+    if idx is None:
+        idx = np.arange(n_stream, dtype=np.int64)
+    if groups is None:
+        n_groups = 1 if n_groups is None else int(n_groups)
+        lab = np.zeros(idx.size, dtype=np.int64)
+    else:
+        lab = groups.detach().cpu().numpy() if isinstance(groups, _torch().Tensor) else np.asarray(groups)
+        if lab.ndim != 1 or lab.size != idx.size or (lab.size and lab.dtype.kind not in "iu"):
+            raise ValueError(f"groups should hold one integer label per selected stream ({idx.size})")
+        lab = lab.astype(np.int64)
+        if n_groups is None:
+            if lab.size and lab.min() < 0:
+                raise ValueError("groups holds a negative label")
+            n_groups = int(lab.max()) + 1 if lab.size else 1
+    perm, rows, count = xsum_plan(lab, n_groups)
+    return first, last, int(n_groups), idx[perm], rows, count
+
+
+def _xsum_outputs(n_groups, n, squares, dev):
+    torch = _torch()
+    mk = lambda: torch.empty((n_groups, n), dtype=torch.int64, device=dev)  # noqa: E731
+    return mk(), (mk() if squares else None), (mk() if squares else None)
+
+
+def common_mode_flac_device(compressed, starts, nbytes, stream_size, groups=None, n_groups=None, first_sample=0, last_sample=None,
+                            streams=None, squares=True, is_int64=False, verify=None, max_temp_bytes=None):
+    """Per-sample sums ACROSS device-resident streams, without a decoded copy (fa_xsum_i32_device / fa_xsum_i64_device):
+    for every group g and every sample j of [first_sample, last_sample) (default: everything; an empty range gives
+    (G, 0) tensors) the sum over the group's streams of what they decode to at j.  `streams`: 1-D flat stream indices, no
+    repeats (default: all).  `groups`: None for one group, or one integer label in [0, n_groups) per selected stream, in
+    any order; n_groups defaults to the largest label + 1 and groups may be empty.
+
+    Returns (sum, sumsq_hi, sumsq_lo): int64 device tensors of shape (G, n) over the decoded INTEGERS (for a float store
+    the quantised ones).  sum equals np.sum(x[sel_g], axis=0, dtype=np.int64) -- exact for one-channel streams, modulo
+    2^64 for two-channel ones (is_int64); the limbs (None for two-channel streams or squares=False) are the exact sums of
+    x*x >> 32 and x*x mod 2^32, as reduce_flac_device's.  The tensors are zero-filled by the library.
+
+    One-channel streams are summed inside the decoder: a wavefront decodes the same frame of 64 streams of one group and
+    folds every column of its tile across its lanes (K7X), adding to the result with 64-bit atomics: at 4096 x 2^20 int32
+    6.95 ms with one group, 7.11 with 64 groups of 64, 6.43 with squares=False (the bare decode: 6.41 ms; decoding 512 rows
+    at a time and accumulating torch.sum(dim=0): 28-37 ms and 3-6 GiB; profiles/common_mode.md).  Two-channel streams go through decoded column chunks under `max_temp_bytes` (default
+    256 MiB), as reduce_flac_device's do, and are SLOWER than decode_flac_device followed by torch.sum(dim=0) where the
+    decoded copy fits (1024 x 2^20 int64: 65 ms against 12.5; 12.8 with a cap that holds the whole range).  All streams
+    must share one block size.  Argument errors raise ValueError
+    before any GPU work, decode failures the decoder's RuntimeError."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64:
+        raise ValueError("starts and nbytes should be of type int64")
+    if starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes must have the same shape")
+    n_stream = int(np.prod(starts.shape))
+    if n_stream <= 0:
+        raise ValueError("starts needs at least one stream")
+    first, last, G, order, rows, _ = _xsum_args(n_stream, stream_size, groups, n_groups, first_sample, last_sample, streams, squares, is_int64)
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("common_mode_flac_device needs compressed, starts and nbytes on the same GPU")
+    sm, qh, ql = _xsum_outputs(G, last - first, squares, dev)
+    if last == first:
+        return sm, qh, ql
+    d_order = torch.from_numpy(order).to(dev)
+    d_rows = torch.from_numpy(rows).to(dev)
+    cap = 0 if max_temp_bytes is None else int(max_temp_bytes)
+    L = _lib.lib()
+    with _on_device(dev):
+        if is_int64:
+            errcode = L.fa_xsum_i64_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                           int(order.size), _dp(d_order), int(rows.shape[0]), _dp(d_rows), G, cap, _dp(sm), _stream_ptr(),
+                                           _verify_arg(verify))
+        else:
+            errcode = L.fa_xsum_i32_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                           int(order.size), _dp(d_order), int(rows.shape[0]), _dp(d_rows), G, _dp(sm), _dp(qh), _dp(ql),
+                                           _stream_ptr(), _verify_arg(verify))
+    if errcode != 0:
+        raise RuntimeError(f"Decoding failed, return code = {errcode}")
+    return sm, qh, ql
+
+
 def _histogram_args(rows, lo, shift, nbins):
     """The argument checks of the value histogram (ValueError, before anything touches the GPU): `nbins` in 1..2048, `lo`
     and `shift` Python integers or integer arrays / tensors of length `rows`, lo inside int64, shift in 0..63.  Returns
@@ -1817,6 +1932,29 @@ class DeviceDecodeIndex:
         if errcode != 0:
             raise RuntimeError(f"Decoding failed, return code = {errcode}")
         return mn, mx, sm, qh, ql
+
+    def common_mode(self, groups=None, n_groups=None, first_sample=0, last_sample=None, streams=None, squares=None, verify=None,
+                    max_temp_bytes=None):
+        """common_mode_flac_device on the indexed store (fa_xsum_indexed): nothing is parsed again.  Returns (sum, sumsq_hi,
+        sumsq_lo), int64 tensors of shape (G, n); the limbs are None for two-channel streams or squares=False (squares=None:
+        whatever the store carries)."""
+        if squares is None:
+            squares = not self.is_int64
+        first, last, G, order, rows, _ = _xsum_args(self.n_stream, self.stream_size, groups, n_groups, first_sample, last_sample, streams,
+                                                    squares, self.is_int64)
+        sm, qh, ql = _xsum_outputs(G, last - first, squares, self.device)
+        if last == first:
+            return sm, qh, ql
+        torch = _torch()
+        d_order = torch.from_numpy(order).to(self.device)
+        d_rows = torch.from_numpy(rows).to(self.device)
+        with _on_device(self.device):
+            errcode = self._L.fa_xsum_indexed(self._h, first, last, int(order.size), _dp(d_order), int(rows.shape[0]), _dp(d_rows), G,
+                                              0 if max_temp_bytes is None else int(max_temp_bytes), _dp(sm), _dp(qh), _dp(ql), _stream_ptr(),
+                                              _verify_arg(verify))
+        if errcode != 0:
+            raise RuntimeError(f"Decoding failed, return code = {errcode}")
+        return sm, qh, ql
 
     def histogram(self, lo, shift, nbins, first_sample=0, last_sample=None, streams=None, verify=None, max_temp_bytes=None):
         """histogram_flac_device on the indexed store (fa_histogram_indexed): nothing is parsed again.  Returns (counts

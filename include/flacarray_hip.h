@@ -413,6 +413,35 @@ int fa_reduce_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const in
 int fa_reduce_indexed(void* index, int64_t first, int64_t last, int64_t width, int64_t n_sel, const int64_t* d_sel_streams, int64_t max_temp_bytes,
                       int64_t* d_min, int64_t* d_max, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
 
+/* ---- fold across streams: per-sample sums over groups of streams, without a decoded copy.  Store, range [first, last)
+ * (both negative: the whole stream), max_temp_bytes, `verify`, errors and stream ordering are fa_reduce_*'s.  The caller
+ * hands in a plan of n = last - first columns, two DEVICE arrays of int64:
+ *   d_order [n_sel]     the selected streams (no repeats), sorted by the group they belong to;
+ *   d_rows [n_rows][3]  one row per 64 lanes of one group -- its group in [0, n_groups), the position in d_order of its
+ *                       first stream, and how many of its 64 lanes are real (1..64); the rows of a group are adjacent
+ *                       and together cover the group's streams once.  An empty group has no row.
+ * An entry outside these bounds, or a stream outside [0, n_stream), is FA_ERROR_DECODE_SAMPLE_RANGE and is not added.
+ * Outputs, device, [n_groups][n] in C order: d_sum (int64: the sum over the group's streams of sample first + j, exact for
+ * one-channel streams, modulo 2^64 for two-channel ones) and for one-channel streams d_sq_hi / d_sq_lo (NULL together: not
+ * wanted), the two exact limbs of the sum of squares in radix 2^32 as fa_reduce_* define them.  The call zero-fills the
+ * outputs itself (the caller need not), but only after its arguments are accepted: a call refused with
+ * FA_ERROR_CONVERT_TYPE, FA_ERROR_DECODE_SAMPLE_RANGE (an empty or misplaced range), FA_ERROR_ZERO_NSTREAM or
+ * FA_ERROR_DECODE_STREAMSIZE has written nothing.  n_sel == 0 leaves zeros.
+ * One-channel streams are summed inside the decoder: a wavefront decodes the same frame of the 64 streams of one plan row
+ * and folds each column of its tile across its lanes, adding to the outputs with 64-bit atomics (integer adds commute:
+ * the result does not depend on the order of arrival).  Two-channel streams go through decoded column chunks under
+ * max_temp_bytes.  fa_xsum_indexed is the same on the store of a decode index (either channel count; d_sq_hi / d_sq_lo
+ * NULL, and max_temp_bytes used, for two channels only).  Everything is issued on `stream`, which is synchronised before
+ * returning. ---- */
+int fa_xsum_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                       int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                       const int64_t* d_rows, int64_t n_groups, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
+int fa_xsum_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                       int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                       const int64_t* d_rows, int64_t n_groups, int64_t max_temp_bytes, int64_t* d_sum, void* stream, int verify);
+int fa_xsum_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows, const int64_t* d_rows,
+                    int64_t n_groups, int64_t max_temp_bytes, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
+
 /* ---- value histogram: counts per value bin of what the streams decode to, without a decoded copy.  Store, range, rows
  * (d_sel_streams / n_sel), max_temp_bytes, `verify`, errors and stream ordering are fa_reduce_*'s.  Every row r has its own
  * d_lo[r] (int64) and d_shift[r] (int32, 0..63), DEVICE arrays of `rows` elements; the call has one nbins, 1..2048
