@@ -34,6 +34,10 @@ __device__ __forceinline__ double std_sub(double a, double b) { return __dsub_rn
 __device__ __forceinline__ float std_mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ double std_mul(double a, double b) { return __dmul_rn(a, b); }
 
+#ifndef FA_STD_MUTANT
+#define FA_STD_MUTANT 0  // test-the-tests builds only (results are wrong, every access stays in bounds; profiles/std_edges.md)
+#endif
+
 // the element the pass sums: x itself, or dtype(dtype(x - mean)^2) (numpy: `x = arr - arrmean; x = x * x`)
 template <typename T, bool DEV>
 __device__ __forceinline__ T std_elem(T x, T mean) {
@@ -42,12 +46,24 @@ __device__ __forceinline__ T std_elem(T x, T mean) {
     return std_mul(d, d);
 }
 
+#if (FA_STD_MUTANT & 32)  // the deviation's square fused into the add: one rounding where numpy has two
+__device__ __forceinline__ float std_fused(float r, float x, float mean) { const float d = std_sub(x, mean); return __fmaf_rn(d, d, r); }
+__device__ __forceinline__ double std_fused(double r, double x, double mean) { const double d = std_sub(x, mean); return __fma_rn(d, d, r); }
+#define FA_STD_ACC(r, x) (DEV ? std_fused(r, x, mean) : std_add(r, x))
+#else
+#define FA_STD_ACC(r, x) std_add(r, std_elem<T, DEV>(x, mean))
+#endif
+
 // numpy's pairwise_sum of one leaf (n <= 128) read element by element from global memory
 template <typename T, bool DEV>
 __device__ T std_leaf_global(const T* __restrict__ a, int n, T mean) {
     if (n < 8) {
+#if (FA_STD_MUTANT & 64)
+        T res = (T)0.0;
+#else
         T res = (T)-0.0;
-        for (int i = 0; i < n; ++i) res = std_add(res, std_elem<T, DEV>(a[i], mean));
+#endif
+        for (int i = 0; i < n; ++i) res = FA_STD_ACC(res, a[i]);
         return res;
     }
     T r[8];
@@ -56,10 +72,10 @@ __device__ T std_leaf_global(const T* __restrict__ a, int n, T mean) {
     const int stop = n - (n % 8);
     for (int i = 8; i < stop; i += 8) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = std_add(r[j], std_elem<T, DEV>(a[i + j], mean));
+        for (int j = 0; j < 8; ++j) r[j] = FA_STD_ACC(r[j], a[i + j]);
     }
     T res = std_add(std_add(std_add(r[0], r[1]), std_add(r[2], r[3])), std_add(std_add(r[4], r[5]), std_add(r[6], r[7])));
-    for (int i = stop; i < n; ++i) res = std_add(res, std_elem<T, DEV>(a[i], mean));
+    for (int i = stop; i < n; ++i) res = FA_STD_ACC(res, a[i]);
     return res;
 }
 
@@ -87,7 +103,11 @@ FA_GLOBAL __global__ __launch_bounds__(64) void stream_chunk_sum_kernel(const T*
     const T mean = DEV ? means[s] : (T)0;
     T total;
 
+#if (FA_STD_MUTANT & 128)  // the fast path only where the chunk itself is 8192 (the host builds no plan for a piece of 8192)
+    if (m == kStdFastChunk && chunk == kStdFastChunk) {
+#else
     if (m == kStdFastChunk) {
+#endif
         // ---- lane-per-leaf path: ROUNDS x (64 rows of 512 B) through LDS ----
         constexpr int EPU = 16 / sizeof(T);        // elements per 16-byte unit
         constexpr int ROUNDS = sizeof(T) / 4;      // 1 (float32) or 2 (float64)
@@ -127,9 +147,8 @@ FA_GLOBAL __global__ __launch_bounds__(64) void stream_chunk_sum_kernel(const T*
 #pragma unroll
                 for (int q = 0; q < EPU; ++q) {
                     const int j = (k * EPU + q) & 7;  // accumulator of this element
-                    const T x = std_elem<T, DEV>(e[q], mean);
-                    if (rd == 0 && k * EPU + q < 8) r[j] = x;  // numpy: r[j] = a[j]
-                    else r[j] = std_add(r[j], x);
+                    if (rd == 0 && k * EPU + q < 8) r[j] = std_elem<T, DEV>(e[q], mean);  // numpy: r[j] = a[j]
+                    else r[j] = FA_STD_ACC(r[j], e[q]);
                 }
             }
         }
@@ -138,7 +157,11 @@ FA_GLOBAL __global__ __launch_bounds__(64) void stream_chunk_sum_kernel(const T*
         for (int off = 1; off < 64; off <<= 1) total = std_add(total, __shfl_xor(total, off, 64));
     } else {
         // ---- plan path ----
+#if (FA_STD_MUTANT & 2)
+        const StdPlanRef& p = plan_tail;
+#else
         const StdPlanRef& p = (m == chunk) ? plan_full : plan_tail;
+#endif
         T* sums = reinterpret_cast<T*>(lds);
         T* stack = sums + kStdPlanLeaves;
         __shared__ int s_op, s_sp;
@@ -152,7 +175,11 @@ FA_GLOBAL __global__ __launch_bounds__(64) void stream_chunk_sum_kernel(const T*
             }
             __syncthreads();
             if (lane == 0) {  // run the program up to the first push of a leaf beyond this batch
+#if (FA_STD_MUTANT & 1)  // the stack pointer is not carried over a batch edge (the stack sits behind 2048 sums in LDS)
+                int op = s_op, sp = 0, k = base;
+#else
                 int op = s_op, sp = s_sp, k = base;
+#endif
                 for (; op < p.n_ops; ++op) {
                     if (p.ops[op]) {
                         if (k == base + nb) break;
@@ -179,13 +206,29 @@ FA_GLOBAL __global__ __launch_bounds__(256) void stream_fold_kernel(const T* __r
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= n_stream) return;
     const T* __restrict__ cs = chunk_sums + s * cps;
+#if (FA_STD_MUTANT & 64)
+    T acc = (T)-0.0;
+#else
     T acc = (T)0;
+#endif
+#if (FA_STD_MUTANT & 4)
+    for (int64_t c = cps - 1; c >= 0; --c) acc = std_add(acc, cs[c]);
+#else
     for (int64_t c = 0; c < cps; ++c) acc = std_add(acc, cs[c]);
+#endif
+#if (FA_STD_MUTANT & 8)
+    const T q = sizeof(T) == 4 ? (T)__fdiv_rn((float)acc, (float)stream_size) : (T)__ddiv_rn((double)acc, (double)stream_size);
+#else
     const T q = (T)__ddiv_rn((double)acc, (double)stream_size);  // numpy divides by an intp: in float64, then rounds
+#endif
     // sqrt correctly rounded: hipcc lowers __fsqrt_rn to a bare v_sqrt_f32 (1 ulp), so float32 takes the float64 one (a
     // division-free Newton expansion that rounds correctly) and rounds that once more -- innocuous for a square root,
     // since 53 >= 2 * 24 + 2 bits
+#if (FA_STD_MUTANT & 16)
+    if (DEV) out[s] = sizeof(T) == 4 ? (T)__fsqrt_rn((float)q) : (T)__dsqrt_rn((double)q);
+#else
     if (DEV) out[s] = (T)__dsqrt_rn((double)q);
+#endif
     else out[s] = q;
 }
 
