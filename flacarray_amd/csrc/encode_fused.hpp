@@ -32,6 +32,13 @@
 
 namespace fa {
 
+// sad_u32 (encode_kernels.hpp) with the subtrahend in a scalar register
+__device__ __forceinline__ uint32_t sad_u32_s(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_sad_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+
 constexpr int kFSmpWords = 65 * 32;  // zero history chunk + 64 chunks of the first half
 #ifndef FA_F_SCANW
 #define FA_F_SCANW 4  // size words per lane and scanner step (x 64 = entries per step)
@@ -59,6 +66,10 @@ constexpr int kFCrcXpow = 520;                                  // x^(8 (i - 255
 #ifndef FA_F_CEIL
 #define FA_F_CEIL 1  // the sample seeds the prediction chain, r = ceil(x - sum): one instruction per sample fewer.  Slower or flat in
                      // rounds 2-3 (the kernel was not issue bound then); -1.6 % since the wait for the offset is gone (r04o)
+#endif
+#ifndef FA_F_ALTSIGN
+#define FA_F_ALTSIGN 1  // the narrow FIXED analysis keeps (-1)^t e_k(t), biased by 2^(27 + k): each further order is one add, 10 vector
+                        // instructions a sample instead of 12.  0: the chain of differences (the A/B).
 #endif
 #ifndef FA_F_BFLY_N
 #define FA_F_BFLY_N 1  // the nine lag sums step by step side by side (one LDS round trip for all swizzles) instead of one after the other
@@ -630,6 +641,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
             FA_IMAGE_ADDRS;
             const uint32_t BIAS = 0x80000000u;
             uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+#if FA_F_ALTSIGN
+            // The chain keeps G_k(t) = B_k + (-1)^t e_k(t) in place of the difference e_k(t), with the bias B_k = 2^(27 + k):
+            // e_k(t) - e_k(t-1) = (-1)^t (g_k(t) + g_k(t-1)), so the next order is the SUM of two biased values and the
+            // biases add up to the next one, G_{k+1}(t) = G_k(t) + G_k(t-1): one two-operand add, and its result is already
+            // what v_sad_u32 needs, |G_k(t) - B_k| = |e_k(t)| (B_k in a scalar register).  1 + 4 + 5 = 10 instructions a
+            // sample instead of 12, and only the five v_sad_u32 are of the slow three-operand class.  A lane's chunks start
+            // at even sample indices and a group is four samples: the parity of t is that of e.  |x| <= 2^24 on this path,
+            // so |e_k| <= 2^(24 + k) < B_k: 0 <= G_k < 2^32, nothing wraps and the unsigned difference is the magnitude.
+            constexpr uint32_t B0 = 1u << 27, B1 = 1u << 28, B2 = 1u << 29, B3 = 1u << 30, B4 = 1u << 31;
+            uint32_t g0, g1, g2, g3;  // G_0 .. G_3 of the sample before (odd t)
+            auto seed = [&](const int4& hh) __attribute__((always_inline)) {
+                const uint32_t d1 = (uint32_t)hh.z - (uint32_t)hh.w, d2 = (uint32_t)hh.z - (uint32_t)hh.y;
+                const uint32_t d3 = (uint32_t)hh.x - (uint32_t)hh.y;
+                g0 = B0 - (uint32_t)hh.w;
+                g1 = B1 + d1;
+                g2 = B2 + (d1 + d2);
+                g3 = B3 + (d1 + d2 + d2 + d3);
+            };
+            auto group = [&](auto mask_tag, const int4& xv, int gi0) __attribute__((always_inline)) {
+                constexpr bool MASK = decltype(mask_tag)::value;
+                const int xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t x = (uint32_t)xs[e];
+                    const uint32_t c0 = (e & 1) ? B0 - x : B0 + x;
+                    const uint32_t c1 = c0 + g0;
+                    const uint32_t c2 = c1 + g1;
+                    const uint32_t c3 = c2 + g2;
+                    const uint32_t c4 = c3 + g3;
+                    const uint32_t n0 = sad_u32_s(c0, B0, s0);
+                    const uint32_t n1 = sad_u32_s(c1, B1, s1);
+                    const uint32_t n2 = sad_u32_s(c2, B2, s2);
+                    const uint32_t n3 = sad_u32_s(c3, B3, s3);
+                    const uint32_t n4 = sad_u32_s(c4, B4, s4);
+                    if constexpr (MASK) {
+                        const int gi = gi0 + e;
+                        s0 = n0;
+                        s1 = (gi >= 1) ? n1 : s1;
+                        s2 = (gi >= 2) ? n2 : s2;
+                        s3 = (gi >= 3) ? n3 : s3;
+                        s4 = (gi >= 4) ? n4 : s4;
+                    } else {
+                        s0 = n0; s1 = n1; s2 = n2; s3 = n3; s4 = n4;
+                    }
+                    g0 = c0; g1 = c1; g2 = c2; g3 = c3;
+                }
+            };
+#else
             int p1, pe1, pe2, pe3;
             auto seed = [&](const int4& hh) __attribute__((always_inline)) {
                 p1 = hh.w;
@@ -663,6 +722,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MLO > 8 ? 2
                     p1 = x; pe1 = e1; pe2 = e2; pe3 = e3;
                 }
             };
+#endif
             // |e_k| < 2^28: a 16-sample u32 partial sum cannot overflow; folded into 64 bits every four groups
             uint64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
             auto fold = [&]() __attribute__((always_inline)) {
