@@ -77,6 +77,9 @@ SYMBOLS = [
     "fa_xsum_i32_device",
     "fa_xsum_i64_device",
     "fa_xsum_indexed",
+    "fa_dot_i32_device",
+    "fa_dot_i64_device",
+    "fa_dot_indexed",
     "fa_histogram_i32_device",
     "fa_histogram_i64_device",
     "fa_histogram_indexed",
@@ -267,6 +270,12 @@ def lib():
     L.fa_xsum_i64_device.restype = cint
     L.fa_xsum_indexed.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, cint]
     L.fa_xsum_indexed.restype = cint
+    L.fa_dot_i32_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, cint]
+    L.fa_dot_i32_device.restype = cint
+    L.fa_dot_i64_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, cint]
+    L.fa_dot_i64_device.restype = cint
+    L.fa_dot_indexed.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp, cint]
+    L.fa_dot_indexed.restype = cint
     L.fa_histogram_i32_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, cint]
     L.fa_histogram_i32_device.restype = cint
     L.fa_histogram_i64_device.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, cint]

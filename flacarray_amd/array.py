@@ -209,6 +209,36 @@ class CrossStreamStats:
 
 
 @dataclass(frozen=True)
+class StreamDots:
+    """Inner products of every stream with K templates (FlacArray.dot): numpy arrays over leading_shape + (K,), or over
+    (len(streams), K) when streams were named; without the K axis when one 1-D template was given.
+
+    exact         object array of Python integers: sum_j x[r, first + j] * T[k, j] over the decoded integers (for a
+                  float store the quantised ones).  Exact whatever the magnitudes.
+    template_sum  object array [K] (a Python integer for a 1-D template): sum_j T[k, j].
+    count         samples in the range, last - first.
+    offsets, gain float64 arrays broadcastable against `exact` (a float store read without quantised=True; else None)."""
+
+    exact: Any
+    template_sum: Any
+    count: int
+    offsets: Any = None
+    gain: Any = None
+
+    def value(self):
+        """float64 inner products.  Integer stores (or quantised=True): float(exact), correctly rounded.  Float stores
+        restore as offset + x / gain, so the product with template k is offset[r] * template_sum[k] + exact[r, k] /
+        gain[r], formed in float64 per row from the exact integers -- every row has its own gain and nothing is mixed.
+        NOT bit-equal to a matmul over the decoded floats, whose every sample was rounded on restore."""
+        ex = np.asarray(self.exact, dtype=object)
+        v = np.asarray(np.frompyfunc(float, 1, 1)(ex), dtype=np.float64) if ex.size else np.zeros(ex.shape, dtype=np.float64)
+        if self.gain is None:
+            return v
+        ts = np.asarray(np.frompyfunc(float, 1, 1)(np.asarray(self.template_sum, dtype=object)), dtype=np.float64)
+        return np.asarray(self.offsets, dtype=np.float64) * ts + v / np.asarray(self.gain, dtype=np.float64)
+
+
+@dataclass(frozen=True)
 class StreamHistogram:
     """Value histogram of a store (FlacArray.histogram): numpy arrays over leading_shape, or over (len(streams),) when
     streams were named.
@@ -745,6 +775,59 @@ class FlacArray:
         sm, qh, ql = (None if t is None else t.cpu().numpy() for t in out)
         limbs = (None, None) if qh is None else (qh.view(np.uint64), ql.view(np.uint64))
         return CrossStreamStats(count, sm, limbs[0], limbs[1], off_mean, gain)
+
+    def dot(self, templates, first=0, last=None, streams=None, quantised=False, verify=None):
+        """Projections without decoding the store into memory (addition to the reference API): the exact inner product
+        of samples [first, last) (default: everything) of every stream, or of the streams named, with each of K integer
+        templates -- a detector's coupling to the common mode common_mode() returned, polynomial or ground-template
+        coefficients, a Fourier coefficient at a chosen frequency.  Returns a StreamDots: `exact` (Python integers, shape
+        leading_shape + (K,), or (len(streams), K) with rows in the order asked), `template_sum`, `count`, and value() in
+        float64.
+
+        `templates`: an integer array or tensor [K, n] or [n] (the K axis is then dropped from the result) with n = last -
+        first exactly; K is unlimited.  Values may span all of int64 -- common_mode().sum passes int32 as soon as a few
+        thousand 24-bit detectors are summed: the host splits such a template into 31-bit limb planes
+        (dot_template_limbs), drops the planes that are all zero, runs the int32 kernel on what is left and recombines in
+        Python integers.  A float template is refused with TypeError (quantise it: np.rint(T * 2**k)), a wrong length with
+        ValueError, before anything touches the GPU.  `streams`: as FlacArray.reduce takes them.
+
+        Float stores: value() is offset[r] * template_sum[k] + exact[r, k] / gain[r] per row (see StreamDots.value);
+        quantised=True gives value() of the integers.
+
+        int32 / float32 stores are multiplied inside the decoder (K7D), 8 template planes per decode of the range and
+        ceil(planes / 8) decodes in all; int64 / float64 stores through decoded column chunks of at most 256 MiB.  What
+        that costs against decode-then-matmul, and from which K on it LOSES: profiles/dot.md.  Uses the resident store
+        and its decode index after to_device(), and uploads the store otherwise.  `verify`: the decoder's frame CRC-16
+        check (None: the process default).  Decode failures raise the decoder's RuntimeError."""
+        from .libflacarray import _dot_args, _dot_templates, dot_exact, dot_flac_device, dot_template_limbs, dot_template_unlimbs
+
+        st = self._st
+        first, last, idx, _ = _dot_args(st.count, st.samples, first, last, streams)
+        T, single = _dot_templates(templates, last - first)
+        K = T.shape[0]
+        planes, index = dot_template_limbs(T)
+        rows = int(idx.size)
+        parts = np.zeros((rows, planes.shape[0]), dtype=object)
+        if rows and planes.shape[0]:
+            sel = None if streams is None else idx
+            if self._resident is not None:
+                out = self._index().dot(planes, first, last, streams=sel, verify=verify)
+            else:
+                _, comp, starts, nbytes = self._device_store()
+                out = dot_flac_device(comp, starts, nbytes, st.samples, planes, first, last, streams=sel, is_int64=st.wide, verify=verify)
+            parts = dot_exact(out) if st.wide else dot_exact(*out)
+        exact = dot_template_unlimbs(parts, index, K)
+        # (exact: the upper words sum inside int64 and the lower ones inside uint64 for any n the call accepts)
+        tsum = np.asarray([int(np.sum(T[k] >> 32, dtype=np.int64)) * (1 << 32) + int(np.sum((T[k] & 0xFFFFFFFF).astype(np.uint64), dtype=np.uint64))
+                           for k in range(K)], dtype=object)
+        lead = tuple(st.lead) if streams is None else (rows,)
+        off = gain = None
+        if st.offsets is not None and not quantised:
+            off = np.asarray(st.offsets).reshape(-1)[idx].astype(np.float64).reshape(lead + (() if single else (1,)))
+            gain = np.asarray(st.gains).reshape(-1)[idx].astype(np.float64).reshape(lead + (() if single else (1,)))
+        if single:
+            return StreamDots(exact.reshape(lead), tsum[0], last - first, off, gain)
+        return StreamDots(exact.reshape(lead + (K,)), tsum, last - first, off, gain)
 
     # ---- distributions: value histogram and exact order statistics from the compressed store ----
     def _hist_pass(self, store, lo, shift, nbins, first, last, idx):

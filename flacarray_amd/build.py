@@ -21,6 +21,7 @@ DEPS = [
     os.path.join(_HERE, "csrc", "histogram_kernels.hpp"),
     os.path.join(_HERE, "csrc", "find_kernels.hpp"),
     os.path.join(_HERE, "csrc", "xsum_kernels.hpp"),
+    os.path.join(_HERE, "csrc", "dot_kernels.hpp"),
     os.path.join(_HERE, "csrc", "scrub_kernels.hpp"),
     os.path.join(_HERE, "csrc", "reindex_kernels.hpp"),
     os.path.join(_HERE, "csrc", "window_kernels.hpp"),

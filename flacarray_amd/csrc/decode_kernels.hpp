@@ -503,13 +503,13 @@ struct DecodeArgs {
     // outputs.  (The unions: the reducing sink, which has no use for the store's, the restore's, the two-channel image's or
     // the compare sink's arguments, keeps its own in their places -- the layout, and with it the code of every other
     // instantiation, is what it was without that sink.)
-    union { int32_t* out_i32; long long* red_min; unsigned long long* hist_counts; long long* find_out; long long* xs_sum; };
-    union { float* out_f32; long long* red_max; unsigned long long* hist_below; long long* find_val; };                 // when non-null: dequantised output instead of out_i32
-    union { const float* offsets; long long* red_sum; unsigned long long* hist_above; const long long* find_lo; unsigned long long* xs_sq_hi; };           // per stream
-    union { const float* gains; unsigned long long* red_sq_hi; const long long* hist_lo; const long long* find_hi; unsigned long long* xs_sq_lo; };
+    union { int32_t* out_i32; long long* red_min; unsigned long long* hist_counts; long long* find_out; long long* xs_sum; unsigned long long* dot_hi; };
+    union { float* out_f32; long long* red_max; unsigned long long* hist_below; long long* find_val; unsigned long long* dot_lo; };                 // when non-null: dequantised output instead of out_i32
+    union { const float* offsets; long long* red_sum; unsigned long long* hist_above; const long long* find_lo; unsigned long long* xs_sq_hi; const int32_t* dot_tmpl; };           // per stream
+    union { const float* gains; unsigned long long* red_sq_hi; const long long* hist_lo; const long long* find_hi; unsigned long long* xs_sq_lo; int64_t dot_ld; };
     int* err;
     // two-channel arrays (NCH == 2): out_i32 is then the task-local planar image
-    union { uint32_t* hibits; unsigned long long* red_sq_lo; const int32_t* hist_shift; const long long* find_ids; };   // [n_tasks][2][hib_words] bit 32 of every sample
+    union { uint32_t* hibits; unsigned long long* red_sq_lo; const int32_t* hist_shift; const long long* find_ids; int64_t dot_rows; };   // [n_tasks][2][hib_words] bit 32 of every sample
     int32_t* assign;    // [n_tasks] channel assignment once both subframes are decoded, else -1
     int32_t hib_words;  // ceil(B / 32)
     int32_t verbatim_done;  // NCH == 2: VERBATIM first subframes (no wasted bits) were decoded by verbatim_channel0_kernel
@@ -538,8 +538,15 @@ struct DecodeArgs {
     // samples [first, last) of the wave's live lanes are added, column by column, to xs_sum[group * n + sample - first] and
     // the radix-2^32 limbs of their squares to xs_sq_hi / xs_sq_lo (null together: no squares).  The arrays hold zeros
     // before the first launch.
-    union { const void* cmp; int64_t red_width; int64_t find_inside; };
-    union { unsigned long long* first_mismatch; int64_t red_nbins; const long long* find_offs; };
+    // dot sink (decode_frames_kernel<..., DOT = KT>; one channel, list mode), K7D: the task table is K7X's with the trivial
+    // plan (one group, rows of 64 consecutive positions of the selection), so a wave holds ONE frame of 64 streams and lane
+    // l of the wave that serves plan row p belongs to result row p * 64 + l (task_out_off is not used).  dot_tmpl is the
+    // template image, int32 [last - first][dot_ld] in C order (sample-major, dot_ld >= dot_k a multiple of 8, padding
+    // columns zero); the pass serves templates dot_k0 .. dot_k0 + KT - 1 (dot_k0 a multiple of KT) and adds, for each one
+    // below dot_k, the two limbs of sum x[first + j] * dot_tmpl[j * dot_ld + k] over the lane's samples to
+    // dot_hi / dot_lo[row * dot_k + k] for rows below dot_rows.  The arrays hold zeros before the first launch.
+    union { const void* cmp; int64_t red_width; int64_t find_inside; int64_t dot_k; };
+    union { unsigned long long* first_mismatch; int64_t red_nbins; const long long* find_offs; int64_t dot_k0; };
 };
 static_assert(sizeof(DecodeArgs) == 216, "DecodeArgs: the sinks share the unions, the layout of the storing decoder's arguments stays");
 
@@ -595,6 +602,11 @@ __device__ __forceinline__ void static_for(F&& f) {
                           // 1 = folds every row, live or not, 2 = does not restore wasted bits, 4 = adds columns outside the valid
                           // range to its nearest end, 32 = does not combine the halves; 8 = xsum_tasks_kernel gives padding lanes
                           // the range; 16 = the driver does not zero-fill
+#endif
+#ifndef FA_DOT_MUTANT
+#define FA_DOT_MUTANT 0  // test-the-tests builds only (results are wrong, every access stays in bounds; profiles/dot.md): K7D
+                         // 1 = the upper limb takes a logical shift, 2 = does not restore wasted bits, 4 = does not take the
+                         // warm-up samples; 8 = the driver's second KT pass starts at k0 = 0 again
 #endif
 #ifndef FA_K7_X
 #define FA_K7_X 0  // timing experiments only (results are wrong): 1 = no prediction, 2 = no global stores, 4 = no tile write,
@@ -831,7 +843,14 @@ __device__ __noinline__ BitsRet slow_sample(const uint8_t* cbase, const uint8_t*
 // tile column are one sample index of 64 streams.  Their sum and the two limbs of their squares are added to the result
 // with 64-bit relaxed atomics of agent scope onto zeroed arrays (integer adds commute, as for K7H).  Only the rows live
 // in this <MO, MO_DONE> pass are folded -- the other rows of the tile hold leftovers -- so the passes add up to the whole.
-template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false, bool HIST = false, int FIND = 0, bool XSUM = false>
+// DOT = KT > 0 (one channel, integers): the dot sink, K7D -- a FOLD sink in K7X's task layout.  The wave holds one frame of
+// 64 streams, so the KT template values of a sample, dot_tmpl[(fstart - first + i) * dot_ld + dot_k0 ..], are the same for
+// all 64 lanes: they are read through a wave-uniform address in the constant address space (scalar loads, no per-lane
+// traffic) and every lane multiplies its sample by them.  p = (int64)x * t is exact; lo += (uint32)p and hi += p >> 32
+// (arithmetic) are kept per template in registers -- a frame has at most 65535 samples, so neither overflows -- and leave
+// with 2 KT 64-bit relaxed atomics of agent scope per lane when the frame is done (the signed limb wraps in two's
+// complement through the same unsigned add).  A lane that is idle, padding, deferred or done by another pass adds nothing.
+template <int MO, int MO_DONE, bool F32, int NCH, bool CMP = false, bool RED = false, bool HIST = false, int FIND = 0, bool XSUM = false, int DOT = 0>
 #ifndef FA_K7_WAVES_ATTR
 #define FA_K7_WAVES_ATTR
 #endif
@@ -847,10 +866,12 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     static_assert(FIND == 0 || (NCH == 1 && !F32 && !CMP && !RED && !HIST), "search sink: one channel, integer domain");
     static_assert(!XSUM || (NCH == 1 && !F32 && !CMP && !RED && !HIST && FIND == 0), "cross-stream sink: one channel, integer domain");
     static_assert(!XSUM || kTileW == 32, "cross-stream sink: a lane owns one of 32 tile columns and one half of the 64 rows");
-    constexpr bool FOLD = RED || HIST || FIND != 0;  // no tile image, no cooperative store: every sample goes to the sink from its register
+    static_assert(DOT == 0 || (NCH == 1 && !F32 && !CMP && !RED && !HIST && FIND == 0 && !XSUM), "dot sink: one channel, integer domain");
+    static_assert(DOT == 0 || (DOT > 0 && DOT <= 8 && 8 % DOT == 0), "dot sink: the pass width divides the template image's alignment");
+    constexpr bool FOLD = RED || HIST || FIND != 0 || DOT != 0;  // no tile image, no cooperative store: every sample goes to the sink from its register
     constexpr bool SINK = CMP && NCH == 1;  // the tile store compares instead of writing
     // one LDS object, so that the ring image starts at LDS address 0 (ring_words builds its addresses with an OR)
-    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + (HIST ? kHistMaxBins : (RED || FIND != 0) ? 0 : kTileW * kLaneStride) + (F32 ? 128 : 0)];
+    __shared__ __attribute__((aligned(16))) uint32_t lds_k7[kDecRingWords * kLaneStride + (HIST ? kHistMaxBins : (RED || FIND != 0 || DOT != 0) ? 0 : kTileW * kLaneStride) + (F32 ? 128 : 0)];
     uint32_t* const rings = lds_k7;
     int32_t* const tile = reinterpret_cast<int32_t*>(lds_k7 + kDecRingWords * kLaneStride);  // sample t of lane l at t*64 + (l ^ 8*(t>>2))
     float2* const row_fg = reinterpret_cast<float2*>(lds_k7 + kDecRingWords * kLaneStride + kTileW * kLaneStride);
@@ -1029,6 +1050,11 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         return (int32_t)v;
     };
 
+    // K7D: the lane's limbs of KT templates, and whether this pass delivers the lane's frame
+    constexpr int KT = DOT != 0 ? DOT : 1;
+    uint64_t dlo[KT];
+    int64_t dhi[KT];
+    bool dot_mine = false;
 #pragma unroll 1
     for (int chn = 0; chn < NCH; ++chn) {
     int lo = 0, hi = 0;  // valid sample range inside this frame
@@ -1259,6 +1285,28 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
         const uint32_t r0h = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)(uint32_t)((uint64_t)row0 >> 32), fl, 64));
         xs_row0 = (int64_t)(((uint64_t)r0h << 32) | r0l);
     }
+    // K7D: whether this pass decodes and delivers the lane's frame (as K7X's live rows); the wave's frame start, made
+    // provably uniform, the range of frame samples that have a template row (the lanes' [lo, hi) lie inside it) and the
+    // element offset of frame sample 0's template values
+    typedef const int32_t __attribute__((address_space(4))) dot_c32;
+    int dot_ulo = 0, dot_uhi = 0;
+    int64_t dot_off0 = 0;
+    if constexpr (DOT != 0) {
+        dot_mine = mode != 3 && hi > lo;
+        const uint32_t fsl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)fstart);
+        const uint32_t fsh = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)fstart >> 32));
+        const int64_t dfs = (int64_t)(((uint64_t)fsh << 32) | fsl);
+        int64_t dl = a.first - dfs, dh = a.first + a.n_decode - dfs;
+        int64_t cap = a.stream_size - dfs;
+        if (cap > a.B) cap = a.B;
+        if (dl < 0) dl = 0;
+        if (dh > cap) dh = cap;
+        if (dh < dl) dh = dl;
+        dot_ulo = (int)dl; dot_uhi = (int)dh;
+        dot_off0 = (dfs - a.first) * a.dot_ld + a.dot_k0;
+#pragma unroll
+        for (int j = 0; j < KT; ++j) { dlo[j] = 0; dhi[j] = 0; }
+    }
     // chunk `pend_ci` is requested one chunk-time before it is stored into the ring
     uint32_t pend_ci = next_chunk;
     Chunk pend = chunk_fetch(cbase, lim16, pend_ci);
@@ -1369,6 +1417,31 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                     if (a.find_val) a.find_val[out_off + find_n] = x;
                     find_n++;
                 }
+            }
+        }
+    };
+
+    // dot sink: sample i of the lane's frame (wasted bits not yet restored) times the KT template values of that sample.
+    // The test and the address are wave-uniform (scalar branch, scalar loads); a lane outside its range multiplies a zero.
+    auto dot_take = [&](int i, int32_t x0) __attribute__((always_inline)) {
+        const int iu = __builtin_amdgcn_readfirstlane(i);
+        if ((uint32_t)(iu - dot_ulo) < (uint32_t)(dot_uhi - dot_ulo)) {
+            dot_c32* const tp = (dot_c32*)a.dot_tmpl + (dot_off0 + (int64_t)iu * a.dot_ld);
+            const bool in = (uint32_t)(i - lo) < (uint32_t)(hi - lo);
+#if (FA_DOT_MUTANT & 2)
+            const int32_t x = in ? x0 : 0;
+#else
+            const int32_t x = in ? (int32_t)((uint32_t)x0 << wasted) : 0;
+#endif
+#pragma unroll
+            for (int j = 0; j < KT; ++j) {
+                const int64_t p = (int64_t)x * (int64_t)tp[j];
+                dlo[j] += (uint32_t)p;
+#if (FA_DOT_MUTANT & 1)
+                dhi[j] += (int64_t)((uint64_t)p >> 32);
+#else
+                dhi[j] += p >> 32;
+#endif
             }
         }
     };
@@ -1524,6 +1597,8 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                 hist_take(i, wrap32(xd));
             } else if constexpr (FIND != 0) {
                 find_take(i, wrap32(xd));
+            } else if constexpr (DOT != 0) {
+                dot_take(i, wrap32(xd));
             } else {
 #if (FA_K7_X & 4)
             if (u == 0)
@@ -1538,6 +1613,10 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
                 if (i < bs) hist_take(i, wrap32(h[u % MO]));  // (as above)
             } else if constexpr (FIND != 0) {
                 if (i < bs) find_take(i, wrap32(h[u % MO]));  // (as above)
+            } else if constexpr (DOT != 0) {
+#if !(FA_DOT_MUTANT & 4)
+                if (i < bs) dot_take(i, wrap32(h[u % MO]));  // (as above)
+#endif
             } else {
             // warm-up sample 16..31 (orders above 16): its value sits in the history
             if (i < bs && i >= kTileW) tile[u * kLaneStride + (lane ^ ((u >> 2) * kTileSwz))] = wrap32(h[u % MO]);
@@ -1888,6 +1967,20 @@ __global__ __launch_bounds__(64) FA_K7_WAVES_ATTR void decode_frames_kernel(Deco
     if constexpr (FIND == 1) {
         // one plain store per frame, by the pass that decoded it (the array holds zeros before the first pass)
         if (find_mine) a.find_out[out_off + (f - a.f0)] = (long long)find_n;
+    }
+    if constexpr (DOT != 0) {
+        // the lane's frame is done: its limbs join the row's (zeros before the first pass; every pass and frame adds)
+        const int64_t row = (task / (64 * a.nfr)) * 64 + lane;
+        if (dot_mine && row < a.dot_rows) {
+#pragma unroll
+            for (int j = 0; j < KT; ++j) {
+                if (a.dot_k0 + j < a.dot_k) {
+                    const int64_t o = row * a.dot_k + a.dot_k0 + j;
+                    (void)__hip_atomic_fetch_add(a.dot_hi + o, (unsigned long long)dhi[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    (void)__hip_atomic_fetch_add(a.dot_lo + o, (unsigned long long)dlo[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
     }
     if constexpr (NCH == 2) {
         if (has_task && task_live) a.assign[task] = ch_assign;  // both subframes decoded

@@ -43,6 +43,7 @@
 #include "histogram_kernels.hpp"
 #include "find_kernels.hpp"
 #include "xsum_kernels.hpp"
+#include "dot_kernels.hpp"
 #include "scrub_kernels.hpp"
 #include "reindex_kernels.hpp"
 #include "window_kernels.hpp"
@@ -568,9 +569,10 @@ struct DecodeIndex {
 // range are folded into where an output would stand.  The rows of the result are all streams (sel == nullptr) or the n_sel
 // streams a device array names; the caller's arrays hold the identities, except the find count's and the cross-stream
 // sums', which the drivers zero.  kXsum: sel is the selection sorted by group (always given) and the rows are its groups.
+// kDot: sel is the selection (always given), one result row per entry, and the plan is the trivial one.
 struct ReduceBins { int64_t width; ReduceOut out; };
 struct FoldSink {
-    enum Kind { kReduce, kHist, kFindCount, kFindFill, kXsum } kind;
+    enum Kind { kReduce, kHist, kFindCount, kFindFill, kXsum, kDot } kind;
     int64_t n_sel;
     const int64_t* sel;
     union {
@@ -578,6 +580,7 @@ struct FoldSink {
         HistOut hist;    // kHist (K7H): hist.nbins value bins per row
         FindSink find;   // kFindCount, kFindFill (K7F): frame_counts, or hit_ids / offs / pos / val
         XsumSink xsum;   // kXsum (K7X): the plan's row table and sum / sq_hi / sq_lo [n_groups][n]
+        DotSink dot;     // kDot (K7D): the trivial plan's row table, the template image and hi / lo [n_sel][K]
     };
 };
 
@@ -774,6 +777,7 @@ void launch_k7(const DecodeArgs& a, int nch, bool cmp, bool f32, const FoldSink*
     else if (fold && fold->kind == FoldSink::kFindCount) FA_K7(false, 1, false, false, false, 1);
     else if (fold && fold->kind == FoldSink::kHist) FA_K7(false, 1, false, false, true);
     else if (fold && fold->kind == FoldSink::kXsum) FA_K7(false, 1, false, false, false, 0, true);
+    else if (fold && fold->kind == FoldSink::kDot) FA_K7(false, 1, false, false, false, 0, false, kDotKT);
     else if (fold) FA_K7(false, 1, false, true);
     else if (cmp) { if (f32) FA_K7(true, 1, true); else FA_K7(false, 1, true); }
     else if (f32) FA_K7(true, 1);
@@ -981,6 +985,10 @@ int decode_device_impl(const DecodeRequest& r) {
             const XsumSink& xs = fold->xsum;
             if (!fold->sel || xs.n_rows <= 0 || xs.n_rows > 0x7fffffff / a.nfr) return FA_ERROR_DECODE_SAMPLE_RANGE;
             a.xs_sum = xs.sum; a.xs_sq_hi = xs.sq_hi; a.xs_sq_lo = xs.sq_lo;
+        } else if (fold->kind == FoldSink::kDot) {
+            const DotSink& ds = fold->dot;
+            if (!fold->sel || ds.n_rows <= 0 || ds.n_rows > 0x7fffffff / a.nfr) return FA_ERROR_DECODE_SAMPLE_RANGE;
+            a.dot_hi = ds.hi; a.dot_lo = ds.lo; a.dot_tmpl = ds.tmpl; a.dot_ld = ds.ld; a.dot_rows = fold->n_sel; a.dot_k = ds.K; a.dot_k0 = ds.k0;
         } else if (fold->kind == FoldSink::kHist) {
             const HistOut& ho = fold->hist;
             a.hist_counts = ho.counts; a.hist_below = ho.below; a.hist_above = ho.above; a.hist_lo = ho.lo; a.hist_shift = ho.shift;
@@ -993,6 +1001,7 @@ int decode_device_impl(const DecodeRequest& r) {
         if (fold->sel) a.n_tasks = fold->n_sel * a.nfr;  // list mode; the table is built on the device, below
         if (fold->kind == FoldSink::kFindFill) a.n_tasks = fold->find.n_hit;  // (the frames with a hit, always a list)
         if (fold->kind == FoldSink::kXsum) a.n_tasks = fold->xsum.n_rows * a.nfr * 64;  // (a wave per plan row and frame)
+        if (fold->kind == FoldSink::kDot) a.n_tasks = fold->dot.n_rows * a.nfr * 64;    // (the same layout)
         if (a.n_tasks <= 0 || a.n_tasks > (int64_t)64 * 0x7fffffff) return FA_ERROR_DECODE_SAMPLE_RANGE;
         if (fold->kind == FoldSink::kFindCount && (rc = find_zero_counts(fold->find, rows * a.nfr, st))) return rc;
     }
@@ -1017,6 +1026,11 @@ int decode_device_impl(const DecodeRequest& r) {
             // one frame of the 64 streams of a plan row per wave, output offset group * n
             hipLaunchKernelGGL(xsum_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, fold->sel, fold->n_sel,
                                fold->xsum.rows, fold->xsum.n_rows, fold->xsum.n_groups, n_stream, a.nfr, a.f0, a.first, a.first + a.n_decode,
+                               col[0], col[1], col[2], col[3], col[4], d_err, (int)FA_ERROR_DECODE_SAMPLE_RANGE);
+        else if (fold->kind == FoldSink::kDot)
+            // K7X's layout with one group: one frame of the 64 streams of a plan row per wave (the output offset is not used)
+            hipLaunchKernelGGL(xsum_tasks_kernel, dim3((unsigned)((a.n_tasks + 255) / 256)), dim3(256), 0, st, fold->sel, fold->n_sel,
+                               fold->dot.rows, fold->dot.n_rows, (int64_t)1, n_stream, a.nfr, a.f0, a.first, a.first + a.n_decode,
                                col[0], col[1], col[2], col[3], col[4], d_err, (int)FA_ERROR_DECODE_SAMPLE_RANGE);
         else
             // the named streams: task t = (row t / nfr, frame f0 + t % nfr), output slot row * nbins
@@ -2567,6 +2581,81 @@ int fa_xsum_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, con
     if (!ix) return FA_ERROR_DECODE_INIT;
     return xsum_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, n_sel, d_order, n_rows, d_rows, n_groups, max_temp_bytes, d_sum,
                        d_sq_hi, d_sq_lo, stream, verify);
+}
+
+// ---- projections: exact inner products of every row with K templates, without a decoded copy (profiles/dot.md) --------
+// One-channel streams: the dot sink of K7 (K7D), kDotKT templates per decode of the range.  Two-channel streams: the
+// column chunks of the binned reduction, each folded by dot_chunk_kernel.  The result arrays are zero-filled here, behind
+// every refusal of the arguments: a refused call has written nothing.
+static int dot_device(int nch, DecodeIndex* ix, const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes,
+                      int64_t n_stream, int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                      const int64_t* d_rows, int64_t K, int64_t ld, const int32_t* d_tmpl, int64_t max_temp_bytes, int64_t* d_hi, uint64_t* d_lo,
+                      int64_t* d_out4, void* stream, int verify) {
+    FA_API_LOCK;
+    int rc;
+    if ((rc = reduce_store_args(nch, ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last))) return rc;
+    if (!d_tmpl || (nch == 1 ? (!d_hi || !d_lo) : !d_out4)) return FA_ERROR_CONVERT_TYPE;
+    if (n_sel < 0 || n_rows < 0 || n_sel > n_stream || n_rows != (n_sel + 63) / 64 || (n_sel > 0 && (!d_order || !d_rows))) return FA_ERROR_CONVERT_TYPE;
+    const int64_t n = last - first;
+    // (n <= 2^32 - 1: the lower limb of a cell sums n terms below 2^32)
+    if (n > 0xffffffffll || K < 1 || ld < K || (ld & 7) != 0) return FA_ERROR_DECODE_SAMPLE_RANGE;
+    if (n_sel == 0) return FA_ERROR_NONE;  // (no rows)
+    if (K > INT64_MAX / 32 / n_sel) return FA_ERROR_ALLOC;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t cells_b = (size_t)n_sel * (size_t)K * 8;
+    if (nch == 1) {
+        FA_HIP_TRY(hipMemsetAsync(d_hi, 0, cells_b, st));
+        FA_HIP_TRY(hipMemsetAsync(d_lo, 0, cells_b, st));
+        FoldSink sink;
+        sink.kind = FoldSink::kDot; sink.n_sel = n_sel; sink.sel = d_order;
+        sink.dot.n_rows = n_rows; sink.dot.rows = d_rows; sink.dot.K = K; sink.dot.ld = ld; sink.dot.tmpl = d_tmpl;
+        sink.dot.hi = reinterpret_cast<unsigned long long*>(d_hi); sink.dot.lo = reinterpret_cast<unsigned long long*>(d_lo);
+        // K > kDotKT: one decode of the range per kDotKT templates (the frame CRC-16 check rides with the first)
+        for (int64_t k0 = 0; k0 < K; k0 += kDotKT) {
+#if (FA_DOT_MUTANT & 8)
+            sink.dot.k0 = 0;
+#else
+            sink.dot.k0 = k0;
+#endif
+            if ((rc = fold_device(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, st, k0 == 0 ? verify : 0, sink)))
+                return rc;
+        }
+        return FA_ERROR_NONE;
+    }
+    FA_HIP_TRY(hipMemsetAsync(d_out4, 0, cells_b * 4, st));
+    return reduce_chunks(ix, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_order, max_temp_bytes, st, verify,
+                         [&](const long long* tmp, int64_t at, int64_t end) -> int {
+        const int64_t w = end - at;
+        const int64_t nseg = (w + kReduceSeg - 1) / kReduceSeg;
+        if (n_sel * nseg > 0x7fffffff) return FA_ERROR_ALLOC;
+        hipLaunchKernelGGL(dot_chunk_kernel, dim3((unsigned)(n_sel * nseg)), dim3(64), 0, st, tmp, w, at, first, nseg, d_tmpl, K, ld,
+                           reinterpret_cast<unsigned long long*>(d_out4));
+        return FA_ERROR_NONE;
+    });
+}
+
+int fa_dot_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                      int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                      const int64_t* d_rows, int64_t K, int64_t ld, const int32_t* d_tmpl, int64_t* d_hi, uint64_t* d_lo, void* stream, int verify) {
+    return dot_device(1, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_order, n_rows, d_rows, K, ld,
+                      d_tmpl, 0, d_hi, d_lo, nullptr, stream, verify);
+}
+
+int fa_dot_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                      int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                      const int64_t* d_rows, int64_t K, int64_t ld, const int32_t* d_tmpl, int64_t max_temp_bytes, int64_t* d_out4, void* stream,
+                      int verify) {
+    return dot_device(2, nullptr, d_bytes, n_bytes, d_starts, d_nbytes, n_stream, stream_size, first, last, n_sel, d_order, n_rows, d_rows, K, ld,
+                      d_tmpl, max_temp_bytes, nullptr, nullptr, d_out4, stream, verify);
+}
+
+int fa_dot_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows, const int64_t* d_rows,
+                   int64_t K, int64_t ld, const int32_t* d_tmpl, int64_t max_temp_bytes, int64_t* d_hi, uint64_t* d_lo, int64_t* d_out4,
+                   void* stream, int verify) {
+    DecodeIndex* ix = reinterpret_cast<DecodeIndex*>(index);
+    if (!ix) return FA_ERROR_DECODE_INIT;
+    return dot_device(ix->nch, ix, nullptr, 0, nullptr, nullptr, 0, 0, first, last, n_sel, d_order, n_rows, d_rows, K, ld, d_tmpl, max_temp_bytes,
+                      d_hi, d_lo, d_out4, stream, verify);
 }
 
 // ---- value histogram: counts per value bin of every row, without a decoded copy (profiles/histogram.md) ----------------

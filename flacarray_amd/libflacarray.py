@@ -1519,6 +1519,188 @@ def common_mode_flac_device(compressed, starts, nbytes, stream_size, groups=None
     return sm, qh, ql
 
 
+_INT32_MIN, _INT32_MAX = -(1 << 31), (1 << 31) - 1
+_INT64_MIN, _INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def dot_template_limbs(templates):
+    """The host split of integer templates into what the int32 kernel multiplies (pure: no GPU).  `templates` is an
+    integer array [K, n] with values anywhere in int64.  A template that fits int32 stays as it is, one plane; any other is
+    split T = t0 + t1 * 2^31 + t2 * 2^62 with t0, t1 in [0, 2^31) and t2 in [-2, 1].  Planes that are all zero are dropped.
+    Returns (planes, index): `planes` int32 [M, n], and `index` int64 [M, 2] holding, per plane, the template it belongs
+    to and its limb number j (weight 2^(31 j)).  dot_template_unlimbs is the inverse on the products."""
+    T = np.asarray(templates)
+    if T.ndim != 2:
+        raise ValueError("templates should be a [K, n] array")
+    if T.dtype.kind not in "iu":
+        raise TypeError("templates should be an integer array")
+    if T.dtype.kind == "u" and T.size and int(T.max()) > _INT64_MAX:
+        raise ValueError("templates holds a value outside int64")
+    T = T.astype(np.int64)
+    planes, index = [], []
+    for k in range(T.shape[0]):
+        row = T[k]
+        if row.size == 0 or (int(row.min()) >= _INT32_MIN and int(row.max()) <= _INT32_MAX):
+            if np.any(row != 0):
+                planes.append(row.astype(np.int32))
+                index.append((k, 0))
+            continue
+        for j, limb in enumerate((row & 0x7FFFFFFF, (row >> 31) & 0x7FFFFFFF, row >> 62)):
+            if np.any(limb != 0):
+                planes.append(limb.astype(np.int32))
+                index.append((k, j))
+    return (np.asarray(planes, dtype=np.int32).reshape(len(planes), T.shape[1]), np.asarray(index, dtype=np.int64).reshape(-1, 2))
+
+
+def dot_template_unlimbs(products, index, n_templates):
+    """The inverse of dot_template_limbs on the results: `products` [rows, M] (Python integers, one column per plane) and
+    the split's `index` give the object array [rows, n_templates] of sum_m products[:, m] * 2^(31 j_m) per template.  A
+    template whose planes were all dropped (all zeros) gives 0."""
+    P = np.asarray(products, dtype=object)
+    out = np.zeros((P.shape[0], int(n_templates)), dtype=object)
+    for m, (k, j) in enumerate(np.asarray(index, dtype=np.int64).reshape(-1, 2)):
+        out[:, int(k)] = out[:, int(k)] + P[:, m] * (1 << (31 * int(j)))
+    return out
+
+
+def dot_exact(hi, lo=None):
+    """The exact inner products as an object array of Python integers, from what the device calls return: (hi, lo)
+    [rows, K] of a one-channel store -- hi * 2^32 + lo with lo unsigned -- or the [rows, K, 4] array of a two-channel one."""
+    as_np = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)  # noqa: E731
+    signed = lambda a: a.astype(np.int64).astype(object)  # noqa: E731
+    unsigned = lambda a: np.ascontiguousarray(a).view(np.uint64).astype(object)  # noqa: E731
+    if lo is None:
+        o = as_np(hi)
+        low = signed(o[..., 0]) * (1 << 32) + unsigned(o[..., 1])
+        high = signed(o[..., 2]) * (1 << 32) + unsigned(o[..., 3])
+        return high * (1 << 32) + low
+    return signed(as_np(hi)) * (1 << 32) + unsigned(as_np(lo))
+
+
+def _dot_templates(templates, n):
+    """The `templates` argument of the public calls, checked (TypeError / ValueError, before anything touches the GPU):
+    an integer array or tensor [K, n] or [n].  Returns (int64 numpy array [K, n], whether the K axis was missing)."""
+    T = templates.detach().cpu().numpy() if isinstance(templates, _torch().Tensor) else np.asarray(templates)
+    if T.dtype.kind == "f":
+        raise TypeError("templates should be integers: the products are exact.  Quantise a float template T yourself, "
+                        "np.rint(T * 2**k).astype(np.int64), and divide the result by 2**k")
+    if T.dtype.kind == "O" and T.size and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in T.reshape(-1)):
+        if any(int(v) < _INT64_MIN or int(v) > _INT64_MAX for v in T.reshape(-1)):
+            raise ValueError("templates holds a value outside int64")
+        T = T.astype(np.int64)
+    if T.dtype.kind not in "iu":
+        raise TypeError(f"templates should be an integer array, not {T.dtype}")
+    if T.dtype.kind == "u" and T.size and int(T.max()) > _INT64_MAX:
+        raise ValueError("templates holds a value outside int64")
+    single = T.ndim == 1
+    if single:
+        T = T.reshape(1, -1)
+    if T.ndim != 2 or T.shape[0] < 1:
+        raise ValueError("templates should be an array [K, n] or [n] with at least one template")
+    if T.shape[1] != n:
+        raise ValueError(f"templates hold {T.shape[1]} samples, the range [first, last) has {n}")
+    return T.astype(np.int64), single
+
+
+def _dot_args(n_stream, stream_size, first_sample, last_sample, streams):
+    """The range and selection checks of the projections (ValueError, before anything touches the GPU).  Returns (first,
+    last, order, rows): the selected stream indices (all of them by default) and the trivial plan of fa_dot_*."""
+    stream_size = int(stream_size)
+    if stream_size <= 0:
+        raise ValueError("You must specify the non-zero stream size")
+    first = int(first_sample)
+    last = stream_size if last_sample is None else int(last_sample)
+    if first < 0 or last > stream_size or first >= last:
+        raise ValueError(f"samples [{first}, {last}) are not a non-empty range inside streams of {stream_size} samples")
+    if last - first > 0xFFFFFFFF:
+        raise ValueError("a range of more than 2^32 - 1 samples: split it and add the results")
+    idx = _stream_indices(streams, n_stream)
+    if idx is None:
+        idx = np.arange(n_stream, dtype=np.int64)
+    rows = np.asarray([(0, at, min(64, idx.size - at)) for at in range(0, idx.size, 64)], dtype=np.int64).reshape(-1, 3)
+    return first, last, idx, rows
+
+
+def _dot_i32_templates(templates, n):
+    """The `templates` argument of the device calls, checked (TypeError / ValueError, before anything touches the GPU): an
+    int32 array or tensor [K, n], K >= 1.  Returns it as a tensor."""
+    torch = _torch()
+    T = templates if isinstance(templates, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(templates))
+    if T.dtype != torch.int32:
+        raise TypeError("the device call takes int32 templates: FlacArray.dot splits wider ones (dot_template_limbs), and a "
+                        "float template is quantised by its owner, np.rint(T * 2**k)")
+    if T.ndim != 2 or T.shape[0] < 1 or T.shape[1] != n:
+        raise ValueError(f"templates should be [K, {n}] with at least one template, not {tuple(T.shape)}")
+    return T
+
+
+def _dot_image(T, n, dev):
+    """The device template image of fa_dot_*: int32 [n, ld], sample-major, ld the next multiple of 8 from K, padding
+    columns zero.  `T`: _dot_i32_templates' tensor.  Returns (image, K, ld)."""
+    torch = _torch()
+    K = int(T.shape[0])
+    ld = (K + 7) // 8 * 8
+    img = torch.zeros((n, ld), dtype=torch.int32, device=dev)
+    img[:, :K] = T.to(dev).t()
+    return img, K, ld
+
+
+def dot_flac_device(compressed, starts, nbytes, stream_size, templates, first_sample=0, last_sample=None, streams=None, is_int64=False,
+                    verify=None, max_temp_bytes=None):
+    """Exact inner products of device-resident streams with K templates, without a decoded copy (fa_dot_i32_device /
+    fa_dot_i64_device): dot[r, k] = sum_j x[r, first_sample + j] * templates[k, j] over the decoded INTEGERS (for a float
+    store the quantised ones).  `templates`: an int32 tensor or array [K, n], n = last_sample - first_sample exactly (K is
+    unlimited; wider values: FlacArray.dot, or dot_template_limbs).  `streams`: 1-D flat stream indices, no repeats
+    (default: all), one result row each, in the order given.
+
+    Returns int64 device tensors: (hi, lo) of shape (rows, K) for one-channel streams -- dot = hi * 2^32 + lo with lo
+    read as unsigned -- or one tensor (rows, K, 4) for two-channel streams (is_int64); dot_exact turns either into Python
+    integers.  The tensors are zero-filled by the library.
+
+    One-channel streams are multiplied inside the decoder (K7D): a wavefront decodes the same frame of 64 streams, so a
+    sample's template values are the same for all its lanes and are read once per wave; 8 templates ride with one decode
+    of the range, K templates cost ceil(K / 8) decodes (timings against the bare decode, reduce and decode-then-matmul:
+    profiles/dot.md).  Two-channel streams go through decoded column chunks under `max_temp_bytes` (default 256 MiB).  All
+    streams must share one block size.  Argument errors raise ValueError / TypeError before any GPU work, decode failures
+    the decoder's RuntimeError."""
+    torch = _torch()
+    if compressed.dtype != torch.uint8:
+        raise ValueError("Compressed data should be of type uint8")
+    if starts.dtype != torch.int64 or nbytes.dtype != torch.int64:
+        raise ValueError("starts and nbytes should be of type int64")
+    if starts.shape != nbytes.shape:
+        raise ValueError("starts and nbytes must have the same shape")
+    n_stream = int(np.prod(starts.shape))
+    if n_stream <= 0:
+        raise ValueError("starts needs at least one stream")
+    first, last, order, rows = _dot_args(n_stream, stream_size, first_sample, last_sample, streams)
+    templates = _dot_i32_templates(templates, last - first)
+    if not (compressed.is_contiguous() and starts.is_contiguous() and nbytes.is_contiguous()):
+        raise ValueError("Only C-contiguous arrays are supported")
+    dev = compressed.device
+    if not (compressed.is_cuda and starts.device == dev and nbytes.device == dev):
+        raise RuntimeError("dot_flac_device needs compressed, starts and nbytes on the same GPU")
+    img, K, ld = _dot_image(templates, last - first, dev)
+    shape = (int(order.size), K, 4) if is_int64 else (int(order.size), K)
+    out = [torch.empty(shape, dtype=torch.int64, device=dev) for _ in range(1 if is_int64 else 2)]
+    if order.size:
+        d_order = torch.from_numpy(order).to(dev)
+        d_rows = torch.from_numpy(rows).to(dev)
+        L = _lib.lib()
+        with _on_device(dev):
+            if is_int64:
+                errcode = L.fa_dot_i64_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                              int(order.size), _dp(d_order), int(rows.shape[0]), _dp(d_rows), K, ld, _dp(img),
+                                              0 if max_temp_bytes is None else int(max_temp_bytes), _dp(out[0]), _stream_ptr(), _verify_arg(verify))
+            else:
+                errcode = L.fa_dot_i32_device(_dp(compressed), compressed.numel(), _dp(starts), _dp(nbytes), n_stream, stream_size, first, last,
+                                              int(order.size), _dp(d_order), int(rows.shape[0]), _dp(d_rows), K, ld, _dp(img), _dp(out[0]),
+                                              _dp(out[1]), _stream_ptr(), _verify_arg(verify))
+        if errcode != 0:
+            raise RuntimeError(f"Decoding failed, return code = {errcode}")
+    return out[0] if is_int64 else (out[0], out[1])
+
+
 def _histogram_args(rows, lo, shift, nbins):
     """The argument checks of the value histogram (ValueError, before anything touches the GPU): `nbins` in 1..2048, `lo`
     and `shift` Python integers or integer arrays / tensors of length `rows`, lo inside int64, shift in 0..63.  Returns
@@ -1955,6 +2137,27 @@ class DeviceDecodeIndex:
         if errcode != 0:
             raise RuntimeError(f"Decoding failed, return code = {errcode}")
         return sm, qh, ql
+
+    def dot(self, templates, first_sample=0, last_sample=None, streams=None, verify=None, max_temp_bytes=None):
+        """dot_flac_device on the indexed store (fa_dot_indexed): nothing is parsed again, whatever the number of decodes.
+        Returns (hi, lo), int64 tensors of shape (rows, K), or for two-channel streams one tensor (rows, K, 4)."""
+        first, last, order, rows = _dot_args(self.n_stream, self.stream_size, first_sample, last_sample, streams)
+        templates = _dot_i32_templates(templates, last - first)
+        img, K, ld = _dot_image(templates, last - first, self.device)
+        torch = _torch()
+        shape = (int(order.size), K, 4) if self.is_int64 else (int(order.size), K)
+        out = [torch.empty(shape, dtype=torch.int64, device=self.device) for _ in range(1 if self.is_int64 else 2)]
+        if order.size:
+            d_order = torch.from_numpy(order).to(self.device)
+            d_rows = torch.from_numpy(rows).to(self.device)
+            wide = self.is_int64
+            with _on_device(self.device):
+                errcode = self._L.fa_dot_indexed(self._h, first, last, int(order.size), _dp(d_order), int(rows.shape[0]), _dp(d_rows), K, ld,
+                                                 _dp(img), 0 if max_temp_bytes is None else int(max_temp_bytes), None if wide else _dp(out[0]),
+                                                 None if wide else _dp(out[1]), _dp(out[0]) if wide else None, _stream_ptr(), _verify_arg(verify))
+            if errcode != 0:
+                raise RuntimeError(f"Decoding failed, return code = {errcode}")
+        return out[0] if self.is_int64 else (out[0], out[1])
 
     def histogram(self, lo, shift, nbins, first_sample=0, last_sample=None, streams=None, verify=None, max_temp_bytes=None):
         """histogram_flac_device on the indexed store (fa_histogram_indexed): nothing is parsed again.  Returns (counts

@@ -442,6 +442,43 @@ int fa_xsum_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int6
 int fa_xsum_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows, const int64_t* d_rows,
                     int64_t n_groups, int64_t max_temp_bytes, int64_t* d_sum, uint64_t* d_sq_hi, uint64_t* d_sq_lo, void* stream, int verify);
 
+/* ---- projections: exact inner products of the streams with K templates, without a decoded copy.  Store, range [first,
+ * last) (both negative: the whole stream), max_temp_bytes, `verify`, errors and stream ordering are fa_reduce_*'s; the
+ * selection comes as fa_xsum_*'s plan with ONE group, two DEVICE arrays of int64:
+ *   d_order [n_sel]     the selected streams (no repeats), one result row each, in this order;
+ *   d_rows [n_rows][3]  n_rows = ceil(n_sel / 64) rows [0, 64 * r, min(64, n_sel - 64 * r)].
+ * An entry outside fa_xsum_*'s bounds, or a stream outside [0, n_stream), is FA_ERROR_DECODE_SAMPLE_RANGE and is not added;
+ * no row beyond n_sel is ever written.
+ * d_tmpl, device, is the template image, sample-major: int32 [n][ld] in C order with n = last - first, ld >= K, ld a
+ * multiple of 8 and the padding columns zero; d_tmpl[j * ld + k] is template k at sample first + j.
+ * Outputs, device, C order.  One-channel streams: d_hi (int64) and d_lo (uint64), [n_sel][K], the two radix-2^32 limbs of
+ *     dot[r][k] = sum_j x[d_order[r]][first + j] * d_tmpl[j * ld + k] = d_hi * 2^32 + d_lo,
+ * d_hi the sum of the products' upper words (p >> 32, arithmetic) and d_lo of their lower words: exact.  Two-channel
+ * streams: d_out4 [n_sel][K][4], the limb pairs (hi, lo) of sum xl * t and of sum xh * t with x = xh * 2^32 + xl, xl
+ * unsigned:  dot = ((out[2] * 2^32 + out[3]) * 2^32) + (out[0] * 2^32 + out[1]), out[0] and out[2] signed, out[1] and
+ * out[3] unsigned: exact.
+ * The call zero-fills the outputs itself (the caller need not), but only after its arguments are accepted: a call refused
+ * with FA_ERROR_CONVERT_TYPE (a missing array, n_rows != ceil(n_sel / 64)), FA_ERROR_DECODE_SAMPLE_RANGE (an empty or
+ * misplaced range, last - first > 2^32 - 1, K < 1, ld < K or ld not a multiple of 8), FA_ERROR_ZERO_NSTREAM or
+ * FA_ERROR_DECODE_STREAMSIZE has written nothing.  n_sel == 0 writes nothing.
+ * One-channel streams are multiplied inside the decoder: a wavefront decodes the same frame of 64 streams, so the template
+ * values of a sample are the same for all its lanes and cost no per-lane memory traffic; 8 templates ride with one decode
+ * of the range and K templates cost ceil(K / 8) decodes.  Lanes add their limbs with 64-bit atomics (integer adds commute:
+ * the result does not depend on the order of arrival).  Two-channel streams go through decoded column chunks under
+ * max_temp_bytes.  fa_dot_indexed is the same on the store of a decode index (d_hi / d_lo for one channel, d_out4 and
+ * max_temp_bytes for two; the others may be NULL).  Everything is issued on `stream`, which is synchronised before
+ * returning. ---- */
+int fa_dot_i32_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                      int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                      const int64_t* d_rows, int64_t K, int64_t ld, const int32_t* d_tmpl, int64_t* d_hi, uint64_t* d_lo, void* stream, int verify);
+int fa_dot_i64_device(const unsigned char* d_bytes, int64_t n_bytes, const int64_t* d_starts, const int64_t* d_nbytes, int64_t n_stream,
+                      int64_t stream_size, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows,
+                      const int64_t* d_rows, int64_t K, int64_t ld, const int32_t* d_tmpl, int64_t max_temp_bytes, int64_t* d_out4, void* stream,
+                      int verify);
+int fa_dot_indexed(void* index, int64_t first, int64_t last, int64_t n_sel, const int64_t* d_order, int64_t n_rows, const int64_t* d_rows,
+                   int64_t K, int64_t ld, const int32_t* d_tmpl, int64_t max_temp_bytes, int64_t* d_hi, uint64_t* d_lo, int64_t* d_out4,
+                   void* stream, int verify);
+
 /* ---- value histogram: counts per value bin of what the streams decode to, without a decoded copy.  Store, range, rows
  * (d_sel_streams / n_sel), max_temp_bytes, `verify`, errors and stream ordering are fa_reduce_*'s.  Every row r has its own
  * d_lo[r] (int64) and d_shift[r] (int32, 0..63), DEVICE arrays of `rows` elements; the call has one nbins, 1..2048
